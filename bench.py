@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the CLD latent-diffusion sampling path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload configs1|configs2|configs3|configs4]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload configs1|configs2|configs3|configs4] [--full]
+                    [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 One "step" = one pass of the hot path over one batch of synthetic agents: the full ancestral sampling loop
@@ -17,11 +18,17 @@ Workloads (BASELINE.json `configs`):
             (parallel.shard_scenes) -- strong scaling; one all-gather of [B_local,52,6] per bench step
   configs4: closed loop, the fixed job of 512 scenes x 64 agents sharded by scene; per bench step 20 sim steps x
             (ContextEncoder -> 50 denoising steps -> decode -> VAE encode of the plan -> PPO reward -> all-gather -> world update)
-  configs1: 32 scenes x 32 agents per GPU, 100 steps, CFG off (round 1's headline; reported as a secondary object by default)
+  configs1: 32 scenes x 32 agents per GPU, 100 steps, CFG off (round 1's headline; reported as a secondary object by --full)
 
-Prints ONE JSON line (rank 0): metric = denoising-step.agent/s over the whole job, plus `roofline` (dominant kernel vs.
-the fp32-MFMA peak, timed with HIP events inside the library on the launch stream) and `cpu_baseline` (the oracle on the
-host cores, bounded sample of the same workload; N = 1 only).
+Prints ONE JSON line (rank 0): metric = denoising-step.agent/s over the whole job, `ms_per_step` (one timed step).
+A plain run sets up, warms up, times the K steps and prints that line, nothing else.  `--full` adds what takes work of its
+own: `roofline` (dominant kernel vs. the fp32-MFMA peak, timed with HIP events inside the library on the launch stream
+during the timed steps), `cpu_baseline` (the oracle on the host cores, bounded sample of the same workload; N = 1 only),
+the secondary objects (other BASELINE configurations, the f16x2 mode, the ContextEncoder; N = 1 only) and, for N > 1,
+the committed one-GPU anchor of the scaling curve.
+
+`--dump-outputs DIR` writes what the last timed step returned (x0 / x1 / logp / decoded trajectories; per-sim-step
+outputs of the closed loop) as DIR/<name>.npy, float32; the inputs are seeded, so two builds can be compared array by array.
 """
 import argparse
 import json
@@ -66,13 +73,21 @@ def main():
                     help="conv arithmetic: exact fp32 MFMA, or fp16 hi/lo split operands with fp32 accumulation (include/cld.h)")
     ap.add_argument("--no-context", action="store_true",
                     help="skip the ContextEncoder (producer of cond_feat, SURVEY 8(f-1)): its measurement / its closed-loop stage")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline of the dominant kernel, CPU baseline, secondary "
+                         "objects, committed one-GPU anchor (off by default: a plain run times the headline only)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="headline only: skip the secondary objects (configs1, f16x2 mode, ContextEncoder, configs3 / configs4 single-GPU anchors)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-profile", action="store_true", help="skip the HIP-event timing of the dominant kernel")
+                    help="with --full: skip the secondary objects (configs1, f16x2 mode, ContextEncoder, configs3 / configs4 single-GPU anchors)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-profile", action="store_true", help="with --full: skip the HIP-event timing of the dominant kernel")
     ap.add_argument("--force-dist", action="store_true",
                     help="initialise torch.distributed (backend nccl = RCCL) even at world size 1, so the collective path runs on a one-GPU box")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step returned as DIR/<name>.npy (float32, at most 64 MB in all; "
+                         "a fixed, seeded sample of agents beyond that)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # started bare with --gpus N: launch the N ranks as a CHILD torch.distributed.run (nothing has touched the GPU yet,
@@ -217,6 +232,7 @@ def main():
             return gather_trajectories(traj, gathered if out is None else out) if even else gather_ragged(traj, sizes)
 
         def one_step():
+            """-> the arrays a caller of the path receives (the last sim step's for the closed loop); "traj" always."""
             if closed:      # rollout loop of env_utils.py:255-304 kept on the device (policy.closed_loop_rollout)
                 wpose, c, opos = world0, cs, opos0
                 for _ in range(closed):
@@ -226,18 +242,19 @@ def main():
                     traj = eng.decode(x0, cnd, c, descaled_output=True)
                     # "VAE encode" stage of configs[4]: the plan re-encoded to its latent posterior (context_utils.py:64-70 -> lstm_vae.py:87-99)
                     sa = eng.state_to_state_and_action(traj[..., :2].contiguous(), traj[..., 3:4].contiguous(), c[:, 2].contiguous(), scaled_output=True)
-                    eng.traj2z(sa, cnd, noise=None)
-                    eng.compute_reward(traj, sa, rfa, dmap, opos, oav)          # PPO reward of the plan (guide_dm_trainer.py:104)
+                    _, mu, lv = eng.traj2z(sa, cnd, noise=None)
+                    rew, off, col = eng.compute_reward(traj, sa, rfa, dmap, opos, oav)     # PPO reward of the plan (guide_dm_trainer.py:104)
                     # ONE all-gather per rollout step: plans and the poses they start from travel as one [B_local, 52*6 + 3] block
                     both = gather(torch.cat([traj.reshape(B, -1), wpose], dim=1), gathered_cl)
                     wpose_new, c = eng.world_step(traj, wpose[:, :2].contiguous(), wpose[:, 2].contiguous(), 4)
                     opos = neighbours(both[:, :312].reshape(-1, 52, 6), both[:, 312:], wpose_new)     # next step's reward / observation input
                     wpose = wpose_new
-                return traj
+                return {"cond_feat": cnd if ctx else None, "x0": x0, "traj": traj, "vae_mu": mu, "vae_logvar": lv, "reward": rew, "offroad": off,
+                        "collision": col, "world_pose": wpose, "curr_states": c}
             x0, x1, logp = eng.sample(x_T, cond, noise=noise, non_cond=non_cond, guidance_w=wl["cfg_w"], guidance=guidance)
             traj = eng.decode(x0, cond, cs, descaled_output=True)
-            gather(traj)
-            return traj
+            allt = gather(traj)
+            return {"x0": x0, "x1": x1, "logp": logp, "traj": traj, "traj_all_ranks": allt if distributed else None}
 
         for _ in range(warmup):
             if closed and wl.get("warm_closed"):      # a warm-up of `warm_closed` sim steps instead of a whole closed-loop pass
@@ -251,14 +268,14 @@ def main():
             eng.profile_enable(True)
         t0 = time.perf_counter()
         for _ in range(steps):
-            traj = one_step()
+            outs = one_step()
         fence()
         dt = time.perf_counter() - t0
         if distributed:
             tt = torch.tensor([dt], device=dev, dtype=torch.float64)
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             dt = float(tt.item())
-        assert bool(torch.isfinite(traj).all()), "non-finite trajectories"
+        assert bool(torch.isfinite(outs["traj"]).all()), "non-finite trajectories"
         roof = None
         if profile:
             ms, launches, flop = eng.profile_read()
@@ -303,7 +320,7 @@ def main():
         ev_rows = (B + 15) // 16 * 16          # agents of this rank; a CFG evaluation carries both passes of each
         evalinfo = {"alg_flop_per_agent": ev_alg / ev_rows, "exec_flop_per_agent": ev_ex / ev_rows, "launches": ev_n}
         units = B_total * n * steps * max(1, closed)
-        return {"dt": dt, "B": B, "B_total": B_total, "units": units, "roof": roof, "even": even, "eval": evalinfo}
+        return {"dt": dt, "B": B, "B_total": B_total, "units": units, "roof": roof, "even": even, "eval": evalinfo, "outs": outs}
 
     def describe(wl, name, custom):
         c = "BASELINE configs[%d]" % wl["idx"] + ((" with overrides (%s)" % ", ".join(custom)) if custom else "")
@@ -323,7 +340,7 @@ def main():
     n = wl["denoise"]
     use_ctx = not args.no_context
     eng = make_engine(n, args.precision, context=use_ctx and bool(wl["closed"]), encoder=bool(wl["closed"]))
-    r = run(wl, eng, args.steps, args.warmup, profile=not args.no_profile, use_ctx=use_ctx)
+    r = run(wl, eng, args.steps, args.warmup, profile=args.full and not args.no_profile, use_ctx=use_ctx)
     value = r["units"] / r["dt"]
     passes = 2 if wl["cfg_w"] else 1
     split = eng.precision == "f16x2"
@@ -353,6 +370,10 @@ def main():
         "direct_form_equivalent_tflops": round(value * FLOP_PER_STEP_AGENT * passes / 1e12, 2),
     }
     if distributed:
+        out["distributed"] = {"backend": backend, "world_size_seen": dist.get_world_size(),
+                              "collective": ("all_gather_into_tensor" if r["even"] else "padded all_gather_into_tensor (uneven scene split)")
+                                            + " of [B_local,52,6] once per rollout step; none inside the denoising loop"}
+    if distributed and args.full:
         anchor = None
         try:        # the N = 1 point of the same fixed job, as last committed by a one-GPU run (context for the curve; not measured here)
             import glob
@@ -364,16 +385,16 @@ def main():
                     break
         except Exception:
             pass
-        out["distributed"] = {"backend": backend, "world_size_seen": dist.get_world_size(), "one_gpu_anchor_committed": anchor,
-                              "collective": ("all_gather_into_tensor" if r["even"] else "padded all_gather_into_tensor (uneven scene split)")
-                                            + " of [B_local,52,6] once per rollout step; none inside the denoising loop"}
+        out["distributed"]["one_gpu_anchor_committed"] = anchor
     if r["roof"]:
         out["roofline"] = r["roof"]
-    del eng
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, r["outs"])
+    del eng, r["outs"]
     torch.cuda.empty_cache()
 
     # ---- secondary objects (N = 1 only; never the headline) -----------------------------------------------------------
-    extras = world == 1 and not args.no_extras and not custom and args.precision == "f32"
+    extras = args.full and world == 1 and not args.no_extras and not custom and args.precision == "f32"
 
     def secondary(key, fn):
         try:
@@ -445,13 +466,30 @@ def main():
                             "headline = structured synthetic raster (31 near-empty history planes + 3 semantic planes, "
                             "trajdata_utils.py:409-420); the 6.8 MB raster per agent is read once, in place"}
         secondary("context_encoder", ctx_extra)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(r["B"], wl)
     if rank == 0:
         print(json.dumps(out, ensure_ascii=False), flush=True)
     if distributed:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def dump_outputs(path, arrays, budget=64 << 20):
+    """Write every array of `arrays` (name -> device tensor or None) as <path>/<name>.npy in float32.  If together they pass
+    `budget` bytes, each keeps the same fixed, seeded, sorted sample of its rows (agents, the leading dimension), so two runs
+    with the same arguments write the same elements."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    host = {k: v.detach().float().cpu().numpy() for k, v in arrays.items() if v is not None}
+    total = sum(a.nbytes for a in host.values())
+    for k, a in host.items():
+        if total > budget and a.shape[0] > 1:
+            keep = max(1, int(a.shape[0] * (budget / total) * 0.99))
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(a))
+    print(f"bench: wrote {', '.join(sorted(host))} to {path}" + (" (seeded sample of rows)" if total > budget else ""),
+          file=sys.stderr, flush=True)
 
 
 def pmc_traffic(rows):

@@ -10,17 +10,17 @@ OUT=$R/gpurun_out/r02
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 HL="--steps 1 --warmup 1 --no-cpu-baseline --no-extras"
-python3 $R/bench.py > $OUT/bench_n1.json 2> $OUT/bench_n1.err && \
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kstats -o bench -- python3 $R/bench.py $HL > $OUT/kstats.log 2>&1 && \
+python3 $R/bench.py --full > $OUT/bench_n1.json 2> $OUT/bench_n1.err && \
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kstats -o bench -- python3 $R/bench.py --full $HL > $OUT/kstats.log 2>&1 && \
 bash $R/scripts/trace_unet.sh r02 1024 2048 4096 && \
 python3 $R/scripts/guide_time.py 1024 2048 4096 > $OUT/guide_time.txt 2>&1 && \
 python3 $R/scripts/sweep_batch.py 8 64 128 256 512 768 1024 1536 2048 4096 8192 > $OUT/batch_sweep.txt 2>&1 && \
-python3 $R/bench.py --workload configs1 --no-cpu-baseline --no-extras > $OUT/bench_n1_configs1.json 2> $OUT/err1 && \
-python3 $R/bench.py --workload configs3 --steps 1 --warmup 1 --no-cpu-baseline --no-extras > $OUT/bench_n1_configs3.json 2> $OUT/err3 && \
-python3 $R/bench.py --workload configs4 --scenes 64 --steps 1 --warmup 1 --no-cpu-baseline --no-extras > $OUT/bench_n1_configs4_shard.json 2> $OUT/err4 && \
+python3 $R/bench.py --full --workload configs1 --no-cpu-baseline --no-extras > $OUT/bench_n1_configs1.json 2> $OUT/err1 && \
+python3 $R/bench.py --full --workload configs3 --steps 1 --warmup 1 --no-cpu-baseline --no-extras > $OUT/bench_n1_configs3.json 2> $OUT/err3 && \
+python3 $R/bench.py --full --workload configs4 --scenes 64 --steps 1 --warmup 1 --no-cpu-baseline --no-extras > $OUT/bench_n1_configs4_shard.json 2> $OUT/err4 && \
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kstats_ctx -o ctx -- python3 $R/scripts/ctx_time.py 256 > $OUT/kstats_ctx.log 2>&1 && \
-(CLD_DIST_BACKEND=gloo python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 $R/bench.py --gpus 2 --scenes 64 --steps 1 --warmup 1 --no-cpu-baseline 2> $OUT/err7 | grep "^{" > $OUT/bench_n2_gloo_rehearsal.json) || { echo "bench/stat chain failed"; tail -5 $OUT/*.err $OUT/err* 2>/dev/null; exit 1; }
-ARGS="$R/bench.py --steps 1 --warmup 0 --denoise-steps 10 --no-cpu-baseline --no-profile --no-extras"
+(CLD_DIST_BACKEND=gloo python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 $R/bench.py --full --gpus 2 --scenes 64 --steps 1 --warmup 1 --no-cpu-baseline 2> $OUT/err7 | grep "^{" > $OUT/bench_n2_gloo_rehearsal.json) || { echo "bench/stat chain failed"; tail -5 $OUT/*.err $OUT/err* 2>/dev/null; exit 1; }
+ARGS="$R/bench.py --full --steps 1 --warmup 0 --denoise-steps 10 --no-cpu-baseline --no-profile --no-extras"
 timeout -k 10 300 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU_MFMA_MOPS_F32 GRBM_GUI_ACTIVE --output-format csv -d $OUT/pmc_sq -o p -- python3 $ARGS > $OUT/pmc_sq.log 2>&1 && \
 timeout -k 10 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -o p -- python3 $ARGS > $OUT/pmc_fetch.log 2>&1 && \
 timeout -k 10 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE --output-format csv -d $OUT/pmc_write -o p -- python3 $ARGS > $OUT/pmc_write.log 2>&1 && \

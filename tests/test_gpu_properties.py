@@ -523,17 +523,22 @@ def test_rccl_all_gather_on_device_tensors(precision):
     assert p.returncode == 0 and "RCCL_OK" in p.stdout, p.stdout[-2000:] + p.stderr[-2000:]
 
 
-def test_bench_distributed_branch_runs_on_rccl(precision):
+def test_bench_distributed_branch_runs_on_rccl(precision, tmp_path):
     """bench.py's distributed branch (init_process_group("nccl", device_id=...), the all-gather inside the timed region, the
     max-over-ranks reduction) on a real device: `--force-dist` at world size 1 must report backend nccl and land within 5 % of
     the same run without torch.distributed (configs[2], 2 timed steps; boxes repeat to ~1.5 %).  The closed loop (configs[4]
-    shard, 2 sim steps) runs with the neighbours of sim step s + 1 read from the tensor the all-gather of step s filled."""
+    shard, 2 sim steps) runs with the neighbours of sim step s + 1 read from the tensor the all-gather of step s filled.
+    The plain run also writes its last step's outputs (--dump-outputs): float32, finite trajectories of all 2,048 agents."""
     import json
+    import numpy as np
     if precision != "f32":
         pytest.skip("precision-independent")
     common = ["bench.py", "--steps", "2", "--warmup", "1", "--no-extras", "--no-cpu-baseline", "--no-profile"]
-    plain = _child(common, {})
+    plain = _child(common + ["--dump-outputs", str(tmp_path)], {})
     assert plain.returncode == 0, plain.stderr[-2000:]
+    assert sorted(p.name for p in tmp_path.iterdir()) == ["logp.npy", "traj.npy", "x0.npy", "x1.npy"]
+    traj = np.load(tmp_path / "traj.npy")
+    assert traj.dtype == np.float32 and traj.shape == (2048, 52, 6) and np.isfinite(traj).all()
     forced = _child(common + ["--force-dist"], {"MASTER_PORT": "29542"})
     assert forced.returncode == 0, forced.stderr[-2000:]
     a, b = json.loads(plain.stdout.strip().splitlines()[-1]), json.loads(forced.stdout.strip().splitlines()[-1])

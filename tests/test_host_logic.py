@@ -309,8 +309,35 @@ def test_bench_cli_parses_without_a_gpu():
     """bench.py must import and parse its flags on a CPU-only host (the driver builds here before benching on the GPU box)."""
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0, out.stderr
-    for flag in ("--gpus", "--steps", "--warmup", "--cfg-w", "--guide", "--closed-loop", "--precision", "--no-context"):
+    for flag in ("--gpus", "--steps", "--warmup", "--cfg-w", "--guide", "--closed-loop", "--precision", "--no-context", "--full",
+                 "--dump-outputs"):
         assert flag in out.stdout
+
+
+def test_bench_dump_outputs_is_float32_capped_and_repeatable(tmp_path):
+    """bench.py --dump-outputs: one float32 .npy per returned array (None skipped); past the byte budget every array keeps the
+    same seeded sample of rows, identical from run to run."""
+    import bench
+    g = torch.Generator().manual_seed(0)
+    arrays = {"x0": torch.randn(1000, 52, 4, generator=g), "traj": torch.randn(1000, 52, 6, generator=g),
+              "logp": torch.randn(1000, generator=g, dtype=torch.float64), "x1": None}
+    bench.dump_outputs(str(tmp_path / "whole"), arrays)
+    for k in ("x0", "traj", "logp"):
+        a = np.load(tmp_path / "whole" / (k + ".npy"))
+        assert a.dtype == np.float32 and np.array_equal(a, arrays[k].float().numpy())
+    assert not (tmp_path / "whole" / "x1.npy").exists()
+    budget = 200_000
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), arrays, budget=budget)
+    total = 0
+    for k in ("x0", "traj", "logp"):
+        a, b = np.load(tmp_path / "a" / (k + ".npy")), np.load(tmp_path / "b" / (k + ".npy"))
+        assert np.array_equal(a, b) and 0 < a.shape[0] < 1000 and a.shape[1:] == arrays[k].shape[1:]
+        total += a.nbytes
+    assert total <= budget
+    rows = np.load(tmp_path / "a" / "traj.npy")[:, 0, 0]       # the same agents in every array
+    idx = [int(np.nonzero(arrays["traj"][:, 0, 0].numpy() == r)[0][0]) for r in rows]
+    assert idx == sorted(idx) and np.array_equal(np.load(tmp_path / "a" / "x0.npy"), arrays["x0"].numpy()[idx])
 
 
 def test_minimal_filtering_matrices_of_the_kernels_reproduce_the_direct_form():
