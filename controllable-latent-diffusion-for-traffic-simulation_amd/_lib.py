@@ -111,6 +111,8 @@ SIGNATURES = {
     "cld_debug_lds_floor": (C.c_int, [_P, C.c_size_t]),
     "cld_debug_force_kernel": (C.c_int, [_P, C.c_int32, C.c_int32]),
     "cld_debug_conv5_form": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32]),
+    "cld_debug_context_layer": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int32, C.c_int32, _P]),
+    "cld_debug_context_pass_size": (C.c_int, [C.c_int32]),
     "cld_debug_stamps": (C.c_int, [_P, _P, C.c_int32]),
     "cld_debug_guide_stamps": (C.c_int, [_P]),
     "cld_get_precision": (C.c_int, [_P]),

@@ -1753,6 +1753,27 @@ int context_pass_size(int B) {
     }
     return best;
 }
+
+// The one dispatch of the encoder's convolutions, shared by cld_context_encode and cld_debug_context_layer: the form a test forced
+// (cld_debug_force_kernel(CLD_KERNEL_CONTEXT)) picks F(4x4, 3x3), F(2x2, 3x3) or the implicit GEMM for the stride-1 3x3 layers; the
+// stride-2 3x3 and the 1x1/2 layers have the implicit GEMM only.
+hipError_t context_conv(cld_handle h, const cld_handle_s::Conv2dLayer& l, const float* x, const float* res, float* y, int relu, int n, hipStream_t s) {
+    const bool wino = h->force_kernel[CLD_KERNEL_CONTEXT] != CLD_FORM_DIRECT;
+    const bool wino44 = h->force_kernel[CLD_KERNEL_CONTEXT] != CLD_FORM_WINOGRAD_F2;      // F(4x4, 3x3) at all four map sizes unless F(2x2) is forced
+    if (wino && wino44 && l.ufrag44) return launch_wino44_conv(l.hin, l.cout, WinoArgs{x, l.ufrag44, l.scale, l.shift, res, y, n, relu}, s);
+    if (wino && l.ufrag) return launch_wino_conv(l.hin, l.cout, WinoArgs{x, l.ufrag, l.scale, l.shift, res, y, n, relu}, s);
+    return launch_conv2d(l.kh, l.stride, l.hin, x, l.wfrag, l.scale, l.shift, res, y, n, l.cin, l.cout, relu, s);
+}
+
+// stem + max-pool of n agents: image [n,34,224,224] NCHW -> pooled [n,56,56,64] NHWC; y1 [n,112,112,64] is the direct form's scratch
+hipError_t context_stem(cld_handle h, const float* image, float* y1, float* pooled, int n, hipStream_t s) {
+    if (h->force_kernel[CLD_KERNEL_CONTEXT] == CLD_FORM_DIRECT) {      // the direct form of the encoder: stem and max-pool as two launches
+        hipError_t e = launch_stem_conv(image, h->stem_w, h->stem_scale, h->stem_shift, y1, nullptr, n, s);
+        return e != hipSuccess ? e : launch_maxpool(y1, pooled, n, s);
+    }
+    // max-pool inside the stem's epilogue: [n,112,112,64] is never written
+    return launch_stem_conv(image, h->stem_w, h->stem_scale, h->stem_shift, nullptr, pooled, n, s);
+}
 }
 size_t cld_context_workspace_bytes(cld_handle h, int32_t B) {
     if (!h || B < 1) return 0;
@@ -1775,21 +1796,13 @@ int cld_context_encode(cld_handle h, const float* image, const float* curr_state
     float* buf[3];
     for (int i = 0; i < 3; ++i) buf[i] = y1 + (size_t)cb * kStemFloats + (size_t)i * cb * kActFloats;
     const bool wino = h->force_kernel[CLD_KERNEL_CONTEXT] != CLD_FORM_DIRECT;
-    const bool wino44 = h->force_kernel[CLD_KERNEL_CONTEXT] != CLD_FORM_WINOGRAD_F2;      // F(4x4, 3x3) where the map is whole 4x4 tiles (56x56, 28x28)
     auto run = [&](const cld_handle_s::Conv2dLayer& l, const float* x, const float* res, float* y, int relu, int n) {
-        if (wino && wino44 && l.ufrag44) return launch_wino44_conv(l.hin, l.cout, WinoArgs{x, l.ufrag44, l.scale, l.shift, res, y, n, relu}, s);
-        if (wino && l.ufrag) return launch_wino_conv(l.hin, l.cout, WinoArgs{x, l.ufrag, l.scale, l.shift, res, y, n, relu}, s);
-        return launch_conv2d(l.kh, l.stride, l.hin, x, l.wfrag, l.scale, l.shift, res, y, n, l.cin, l.cout, relu, s);
+        return context_conv(h, l, x, res, y, relu, n, s);
     };
     const int pass = wino ? context_pass_size(B) : cb;
     for (int b0 = 0; b0 < B; b0 += pass) {
         const int n = (B - b0) < pass ? (B - b0) : pass;
-        if (h->force_kernel[CLD_KERNEL_CONTEXT] == CLD_FORM_DIRECT) {      // the direct form of the encoder: stem and max-pool as two launches
-            HIPCK(h, launch_stem_conv(image + (size_t)b0 * 34 * 224 * 224, h->stem_w, h->stem_scale, h->stem_shift, y1, nullptr, n, s));
-            HIPCK(h, launch_maxpool(y1, buf[0], n, s));
-        } else {                                                          // max-pool inside the stem's epilogue: [n,112,112,64] is never written
-            HIPCK(h, launch_stem_conv(image + (size_t)b0 * 34 * 224 * 224, h->stem_w, h->stem_scale, h->stem_shift, nullptr, buf[0], n, s));
-        }
+        HIPCK(h, context_stem(h, image + (size_t)b0 * 34 * 224 * 224, y1, buf[0], n, s));
         int xi = 0;                                            // buffer holding the current block input
         for (int li = 0; li < 4; ++li)
             for (int b = 0; b < 2; ++b) {                      // BasicBlock: relu(bn2(conv2(relu(bn1(conv1 x)))) + identity)
@@ -1822,6 +1835,34 @@ int cld_context_combine(cld_handle h, const float* map_feat, int32_t broadcast, 
     HIPCK(h, launch_context_head(a, static_cast<hipStream_t>(stream)));
     return CLD_OK;
 }
+
+int cld_debug_context_layer(cld_handle h, int32_t layer, const float* x, const float* residual, float* y, int32_t n, int32_t relu, void* stream) {
+    if (!h) return CLD_ERR_ARG;
+    if (!h->finalized || !h->has_context) return fail(h, CLD_ERR_STATE, "cld_debug_context_layer: context_encoder weights not loaded");
+    if (layer < 0 || layer > 19 || !x || !y || n < 1 || n > kCtxChunk || (layer == 0 && (residual || !relu)))
+        return fail(h, CLD_ERR_ARG, "cld_debug_context_layer: bad argument");
+    if (reinterpret_cast<uintptr_t>(x) % 16 || reinterpret_cast<uintptr_t>(y) % 16 || reinterpret_cast<uintptr_t>(residual) % 16)
+        return fail(h, CLD_ERR_ARG, "cld_debug_context_layer: tensors must be 16-byte aligned");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (layer == 0) {
+        float* y1 = nullptr;      // the direct form's [n,112,112,64] scratch
+        if (h->force_kernel[CLD_KERNEL_CONTEXT] == CLD_FORM_DIRECT) HIPCK(h, hipMalloc(reinterpret_cast<void**>(&y1), (size_t)n * kStemFloats * sizeof(float)));
+        const hipError_t e = context_stem(h, x, y1, y, n, s);
+        if (y1) {
+            const hipError_t es = hipStreamSynchronize(s);
+            (void)hipFree(y1);
+            HIPCK(h, es);
+        }
+        HIPCK(h, e);
+        return CLD_OK;
+    }
+    const int li = layer <= 16 ? (layer - 1) / 4 : layer - 16;
+    const cld_handle_s::Conv2dLayer& l = layer <= 16 ? h->rn_conv[li][((layer - 1) / 2) % 2][(layer - 1) % 2] : h->rn_ds[li];
+    HIPCK(h, context_conv(h, l, x, residual, y, relu ? 1 : 0, n, s));
+    return CLD_OK;
+}
+
+int cld_debug_context_pass_size(int32_t B) { return B < 1 ? CLD_ERR_ARG : context_pass_size(B); }
 
 int cld_compute_reward(cld_handle h, const float* traj, const float* traj_scaled, const float* raster_from_agent,
                        const uint8_t* drivable_map, int32_t H, int32_t W, const float* other_pos, const uint8_t* other_avail,

@@ -16,6 +16,14 @@ from ._lib import CldConfig, CldError
 
 T, D, COND = 52, 4, 256
 
+# the layers of the ContextEncoder's ResNet-18 in cld_debug_context_layer's order: (kernel, stride, input map size, C_in, C_out)
+CONTEXT_LAYERS = [(7, 2, 224, 34, 64)]
+for _li in range(4):
+    _c, _hin = 64 << _li, 56 >> max(_li - 1, 0)
+    _s = 1 if _li == 0 else 2
+    CONTEXT_LAYERS += [(3, _s, _hin, _c // _s, _c), (3, 1, _hin // _s, _c, _c), (3, 1, _hin // _s, _c, _c), (3, 1, _hin // _s, _c, _c)]
+CONTEXT_LAYERS += [(1, 2, 56 >> (_li - 1), 32 << _li, 64 << _li) for _li in range(1, 4)]
+
 
 def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else C.c_void_p(t.data_ptr())
@@ -109,6 +117,22 @@ class Engine:
         if which not in _lib.KERNELS or form not in _lib.FORMS:
             raise CldError(f"force_kernel: unknown kernel '{which}' or formulation '{form}'")
         self._check(self.lib.cld_debug_force_kernel(self._h, _lib.KERNELS[which], _lib.FORMS[form]), "cld_debug_force_kernel")
+
+    def debug_context_layer(self, layer: int, x, residual=None, relu: bool = True):
+        """Tests only (cld_debug_context_layer): layer `layer` of the ContextEncoder's ResNet-18 on n <= 256 agents, in the form
+        `force_kernel("context", ...)` holds.  0: the stem, image [n,34,224,224] NCHW -> max-pooled [n,56,56,64] NHWC; 1..16:
+        layer{li+1}.{b}.conv{c+1} + bn for layer = 1 + 4 li + 2 b + c; 17..19: the downsample of layer2..4.  NHWC in and out:
+        y = [relu](bn(conv x) + residual)."""
+        kh, stride, hin, cin, cout = CONTEXT_LAYERS[layer]
+        n = int(x.shape[0])
+        x = self._f32(x, (n, cin, hin, hin) if layer == 0 else (n, hin, hin, cin))
+        ho = 56 if layer == 0 else hin // stride
+        res = None if residual is None else self._f32(residual, (n, ho, ho, cout))
+        y = torch.empty(n, ho, ho, cout, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cld_debug_context_layer(self._h, int(layer), _ptr(x), _ptr(res), _ptr(y), n, int(bool(relu)), self._stream()),
+                        "cld_debug_context_layer")
+        return y
 
     @property
     def loop_steps(self) -> int:

@@ -408,6 +408,73 @@ def resnet18_features(w: Dict[str, Tensor], image: Tensor, taps: Optional[dict] 
     return F.linear(x, w[r + "fc.weight"], w[r + "fc.bias"])
 
 
+def resnet18_layers():
+    """The 20 convolution + BatchNorm layers of `resnet18_features` in the order cld_debug_context_layer numbers them:
+    0 the stem, 1..16 layer{li}.{b}.conv{c} in forward order, 17..19 the downsample of layer2..4 -> [(conv weight key, BN prefix,
+    stride, padding)]."""
+    r = RESNET
+    out = [(r + "conv1.weight", r + "bn1", 2, 3)]
+    for li in range(1, 5):
+        for b in range(2):
+            for c in (1, 2):
+                out.append((f"{r}layer{li}.{b}.conv{c}.weight", f"{r}layer{li}.{b}.bn{c}", 2 if (b == 0 and c == 1 and li > 1) else 1, 1))
+    out += [(f"{r}layer{li}.0.downsample.0.weight", f"{r}layer{li}.0.downsample.1", 2, 0) for li in range(2, 5)]
+    return out
+
+
+def resnet18_layer(w: Dict[str, Tensor], layer: int, x: Tensor, residual: Optional[Tensor] = None, relu: bool = True,
+                   want_bound: bool = False):
+    """One layer of `resnet18_features` in float64, NCHW: y = [relu](bn(conv x) + residual), BatchNorm from its running statistics;
+    the stem (layer 0, always with ReLU) adds the 3x3/2 max-pool.  want_bound: also the per-element magnitude
+    E = |scale| conv(|x|, |w|) + |shift| + |residual| (scale = gamma / sqrt(var + eps), shift = beta - mean scale) that bounds the
+    rounding error of any fp32 evaluation of the layer (after the max-pool: the pool of E; ReLU and max are 1-Lipschitz)."""
+    key, bn, stride, pad = resnet18_layers()[layer]
+    wt, x = w[key].double(), x.double()
+    d = {k: w[bn + k].double() for k in (".weight", ".bias", ".running_mean", ".running_var")}
+    y = F.batch_norm(F.conv2d(x, wt, None, stride=stride, padding=pad), d[".running_mean"], d[".running_var"], d[".weight"], d[".bias"],
+                     False, 0.0, 1e-5)
+    if residual is not None:
+        y = y + residual.double()
+    if relu or layer == 0:
+        y = F.relu(y)
+    if layer == 0:
+        y = F.max_pool2d(y, 3, 2, 1)
+    if not want_bound:
+        return y
+    scale = d[".weight"] / torch.sqrt(d[".running_var"] + 1e-5)
+    shift = d[".bias"] - d[".running_mean"] * scale
+    e = scale.abs()[:, None, None] * F.conv2d(x.abs(), wt.abs(), None, stride=stride, padding=pad) + shift.abs()[:, None, None]
+    if residual is not None:
+        e = e + residual.double().abs()
+    if layer == 0:
+        e = F.max_pool2d(e, 3, 2, 1)
+    return y, e
+
+
+def resnet18_by_layers(w: Dict[str, Tensor], image: Tensor):
+    """`resnet18_features` up to the last BasicBlock composed from the 20 `resnet18_layer` calls, in float64 -> (calls, taps): calls[layer] =
+    (x, residual, relu, y) as the network runs that layer (NCHW), taps = {"pool", "layer1".."layer4"} (pool: the stem's max-pooled output)."""
+    calls = [None] * 20
+    x = image.double()
+    y = resnet18_layer(w, 0, x)
+    calls[0] = (x, None, True, y)
+    taps = {"pool": y}
+    x = y
+    for li in range(4):
+        for b in range(2):
+            l1, l2 = 1 + 4 * li + 2 * b, 2 + 4 * li + 2 * b
+            t = resnet18_layer(w, l1, x)
+            calls[l1] = (x, None, True, t)
+            idt = x
+            if b == 0 and li > 0:
+                idt = resnet18_layer(w, 16 + li, x, relu=False)
+                calls[16 + li] = (x, None, False, idt)
+            x = resnet18_layer(w, l2, t, idt)
+            calls[l2] = (t, idt, True, x)
+        taps[f"layer{li + 1}"] = x
+    return calls, taps
+
+
 def context_encode(w: Dict[str, Tensor], image: Tensor, curr_states: Tensor, taps: Optional[dict] = None) -> Tensor:
     """ContextEncoder.forward (models/context_utils.py:40-61): cond_feat = process_cond_mlp(
     [agent_state_encoder(curr_states) | map_encoder(image)]) -> [B,256].  curr_states [B,4] = (x, y, v, yaw)

@@ -376,3 +376,51 @@ def test_minimal_filtering_matrices_of_the_kernels_reproduce_the_direct_form():
     assert "{-16.0 / 15, -8.0 / 15, -4.0 / 15}, {1.0 / 15, -2.0 / 15, 4.0 / 15}" in src
     for M in (BT, AT, BT6, AT6):                                        # exact in fp32: the kernels apply them with fp32 constants
         assert np.array_equal(M.astype(np.float32).astype(np.float64), M)
+
+
+def test_context_layer_references_compose_to_the_oracle_resnet():
+    """The per-layer fp64 references of the ContextEncoder's ResNet-18 (oracle.resnet18_layer: conv, BatchNorm from its running statistics,
+    + residual, ReLU; the stem's max-pool), chained in the network's order, are the oracle's resnet18_features: its stem (max-pooled) and
+    layer1..4 taps and its fc output, on a dense and a sparse raster.  The GPU tests of cld_debug_context_layer hold every layer to them."""
+    from cld_amd import synth
+    from cld_amd.engine import CONTEXT_LAYERS
+    from oracle import cld_oracle as O
+    w = O.to_torch(synth.make_context_weights(0), dtype=torch.float64)
+    img = torch.from_numpy(np.concatenate([synth.make_raster(1, 5, dense=True), synth.make_raster(1, 6, dense=False)])).double()
+    taps = {}
+    mf = O.resnet18_features(w, img, taps)
+    calls, got = O.resnet18_by_layers(w, img)
+    assert all(c is not None for c in calls)
+    for layer, (x, res, relu, y) in enumerate(calls):      # the table the library's debug surface and its tests share
+        kh, stride, hin, cin, cout = CONTEXT_LAYERS[layer]
+        assert w[O.resnet18_layers()[layer][0]].shape == (cout, cin, kh, kh) and x.shape[1:] == (cin, hin, hin)
+        assert y.shape[1:] == ((cout, 56, 56) if layer == 0 else (cout, hin // stride, hin // stride))
+        assert (res is not None) == (layer in (2, 4, 6, 8, 10, 12, 14, 16)) and relu == (layer < 17)
+        yb, e = O.resnet18_layer(w, layer, x, res, relu, want_bound=True)
+        assert torch.equal(yb, y) and bool((e * (1 + 1e-12) >= y.abs()).all()), layer      # E bounds |y| itself
+    assert torch.equal(got["pool"], torch.nn.functional.max_pool2d(taps["stem"], 3, 2, 1))
+    for k in ("layer1", "layer2", "layer3", "layer4"):
+        assert torch.equal(got[k], taps[k]), k
+    r = O.RESNET
+    assert torch.equal(torch.nn.functional.linear(got["layer4"].mean(dim=(2, 3)), w[r + "fc.weight"], w[r + "fc.bias"]), mf)
+
+
+def test_context_pass_size():
+    """cld_debug_context_pass_size (no device call): one pass up to 256 agents, passes of 128..256 above, and the size the documented cost
+    model of cld_api.hip (generations of 512 workgroups of the four F(4x4) launch kinds, a fixed cost per pass) puts at its minimum."""
+    from cld_amd import _lib
+    lib = _lib.load()
+    assert lib.cld_debug_context_pass_size(0) < 0
+
+    def cost(n):
+        gens = lambda tpa, ncb: ((n * tpa + 15) // 16 * ncb + 511) // 512      # noqa: E731
+        return 4 * gens(196, 1) * 15 + 3 * gens(49, 2) * 27 + 3 * gens(16, 4) * 43 + 3 * gens(4, 8) * 85 + 60
+
+    for B in list(range(1, 300)) + [511, 512, 767, 1000, 1024, 2048, 3000, 4096, 8192, 16384]:
+        p = lib.cld_debug_context_pass_size(B)
+        if B <= 256:
+            assert p == B
+            continue
+        assert 128 <= p <= 256, B
+        total = lambda q: (B // q) * cost(q) + (cost(B % q) if B % q else 0)      # noqa: E731
+        assert total(p) == min(total(q) for q in range(128, 257)), B
