@@ -31,9 +31,28 @@ class CldConfig(C.Structure):
 PRECISIONS = {"f32": 0, "f16x2": 1}
 OPTIMIZERS = {"adam": 0, "sgd": 1}
 KERNELS = {"guide": 0, "decode": 1, "encode": 2, "unet": 3, "context": 4, "conv5": 5}        # cld_debug_force_kernel
-FORMS = {"auto": 0, "valu": 1, "mfma": 2, "quad": 3,         # "quad": guide kernel only
-         "layers": 1, "chain": 2, "chain1": 3, "chain4": 4, "chainw": 5, "chainw2": 6, "chainw1": 7,                              # "unet" only: one launch per layer / LDS-resident layer chains
-         "direct": 1, "winograd": 2, "winograd_whole": 3, "winograd_ksplit": 4, "winograd_f2": 3}                                                     # "context": the 3x3 / stride-1 convolutions of the ResNet-18; "conv5": the 256 -> 256 k5 layers of the U-Net
+# cld_debug_force_kernel: the formulations each kernel has (include/cld.h CLD_FORM_*).  The numbers are reused across kernels (3 is "quad"
+# for the guide kernel, "chain1" for the U-Net, "winograd_f2" for the ContextEncoder and "winograd_whole" for the k5 layers), so a form
+# is named together with its kernel: form_id() refuses a name the kernel does not have.
+KERNEL_FORMS = {
+    "guide": {"auto": 0, "valu": 1, "mfma": 2, "quad": 3},
+    "decode": {"auto": 0, "valu": 1, "mfma": 2},
+    "encode": {"auto": 0, "valu": 1, "mfma": 2},
+    "unet": {"auto": 0, "layers": 1, "chain": 2, "chain1": 3, "chain4": 4, "chainw": 5, "chainw2": 6, "chainw1": 7},      # one launch per layer / LDS-resident layer chains
+    "context": {"auto": 0, "direct": 1, "winograd": 2, "winograd_f2": 3},       # the 3x3 / stride-1 convolutions of the ResNet-18
+    "conv5": {"auto": 0, "direct": 1, "winograd": 2, "winograd_whole": 3, "winograd_ksplit": 4},     # the k5 layers of the U-Net's L = 13 / 26 levels
+}
+FORMS = {name: v for forms in KERNEL_FORMS.values() for name, v in forms.items()}      # every name -> its number (the union of the above)
+
+
+def form_id(kind: str, name: str) -> int:
+    """The CLD_FORM_* number of formulation `name` of kernel `kind`; raises ValueError on a kernel or a name that kernel does not have."""
+    if kind not in KERNEL_FORMS:
+        raise ValueError(f"unknown kernel '{kind}' (one of {sorted(KERNEL_FORMS)})")
+    forms = KERNEL_FORMS[kind]
+    if name not in forms:
+        raise ValueError(f"kernel '{kind}' has no formulation '{name}' (one of {sorted(forms)})")
+    return forms[name]
 
 
 class CldGuidance(C.Structure):
@@ -111,6 +130,8 @@ SIGNATURES = {
     "cld_debug_lds_floor": (C.c_int, [_P, C.c_size_t]),
     "cld_debug_force_kernel": (C.c_int, [_P, C.c_int32, C.c_int32]),
     "cld_debug_conv5_form": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32]),
+    "cld_debug_conv5_items": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.c_int32]),
+    "cld_debug_unet_span": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, C.c_int32, _P, C.c_size_t, _P]),
     "cld_debug_context_layer": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int32, C.c_int32, _P]),
     "cld_debug_context_pass_size": (C.c_int, [C.c_int32]),
     "cld_debug_stamps": (C.c_int, [_P, _P, C.c_int32]),

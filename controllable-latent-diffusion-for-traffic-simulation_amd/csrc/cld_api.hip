@@ -572,16 +572,19 @@ bool chain_wino(cld_handle h, int b_pad) {
     return h->force_kernel[CLD_KERNEL_CONV5] != CLD_FORM_DIRECT;
 }
 
-// One U-Net evaluation (temporal.py:122-180) on the padded latent `x` [b_pad,52,4]; leaves the
-// final_conv.0 activations [b_pad,52,64] in w.buf[7].
-hipError_t run_unet(cld_handle h, const Ws& w, const float* x, int t_idx, int b_pad, hipStream_t s) {
+// One span of a U-Net evaluation (temporal.py:122-180): run_unet is the 12 spans in a row, and cld_debug_unet_span runs one of them
+// alone.  Every form (one launch per layer, the layer chains, the Winograd launches) runs exactly these 12 spans, so the buffer a span
+// writes holds the same tensor in every form.  Span k reads kSpanIn[k] (and the skip kSpanSkip[k]) and writes kSpanOut[k]; -1 is the
+// padded latent w.xw.  Span 11 leaves final_conv.0's activations [b_pad,52,64] in w.buf[7], or the noise prediction itself (eps_in_buf7).
+constexpr int kSpans = 12;
+constexpr int kSpanIn[kSpans] = {-1, 6, 2, 4, 6, 2, 5, 2, 3, 2, 6, 3};
+constexpr int kSpanSkip[kSpans] = {-1, -1, -1, -1, -1, -1, -1, -1, 5, -1, -1, 4};
+constexpr int kSpanOut[kSpans] = {6, 2, 4, 6, 2, 5, 2, 3, 2, 6, 3, 7};
+constexpr int kSpanL[kSpans + 1] = {52, 26, 26, 26, 13, 13, 13, 13, 13, 13, 13, 26, 52};      // rows of a span's input (and of span 11's skip: 26)
+constexpr int kSpanC[kSpans + 1] = {4, 64, 128, 128, 128, 256, 256, 256, 256, 128, 128, 128, 4};   // ... its channels; entry 12: eps
+hipError_t run_unet_span(cld_handle h, const Ws& w, const float* x, int t_idx, int b_pad, int span, hipStream_t s) {
     const float* tbr = t_idx >= 0 ? h->tb + (size_t)t_idx * NCB : nullptr;     // < 0: per-agent timesteps, time bias folded into w.cb
     float* const* b = w.buf;
-    h->launch_counter = 0;
-    h->eval_counter++;
-    h->eval_alg_flop = h->eval_exec_flop = 0.0;
-    h->eval_launches = 0;
-    set_lds_floor(h->lds_floor);
     hipError_t e;
 #define RC(...) do { e = run_conv(h, __VA_ARGS__, w.cb, tbr, b_pad, s); if (e != hipSuccess) return e; } while (0)
     auto resblock = [&](const ResBlock& rb, const float* in1, const float* in2, float* out) -> hipError_t {
@@ -598,6 +601,8 @@ hipError_t run_unet(cld_handle h, const Ws& w, const float* x, int t_idx, int b_
         return hipSuccess;
     };
 #define RB(...) do { e = resblock(__VA_ARGS__); if (e != hipSuccess) return e; } while (0)
+    switch (span) {
+    case 0:
     if (use_chains(h, b_pad)) {
         // downs.0 (five layers at 64 channels x 52 rows) as one launch, the tile resident in LDS (conv_chain.hip)
         ChainHeadArgs ca{};
@@ -637,18 +642,22 @@ hipError_t run_unet(cld_handle h, const Ws& w, const float* x, int t_idx, int b_
     RB(h->blocks[1], b[2], nullptr, b[3]);
     RC(h->down[0], b[3], nullptr, b[6], nullptr);
     }
-    RB(h->blocks[2], b[6], nullptr, b[2]);
-    RB(h->blocks[3], b[2], nullptr, b[4]);            // skip 128@26
-    RC(h->down[1], b[4], nullptr, b[6], nullptr);
-    RB(h->blocks[4], b[6], nullptr, b[2]);
-    RB(h->blocks[5], b[2], nullptr, b[5]);            // skip 256@13
-    RB(h->blocks[6], b[5], nullptr, b[2]);
-    RB(h->blocks[7], b[2], nullptr, b[3]);
-    RB(h->blocks[8], b[3], b[5], b[2]);               // cat(x, skip) 512@13 -> 128@13
-    RB(h->blocks[9], b[2], nullptr, b[6]);
+    break;
+    case 1: RB(h->blocks[2], b[6], nullptr, b[2]); break;
+    case 2: RB(h->blocks[3], b[2], nullptr, b[4]); break;            // skip 128@26
+    case 3: RC(h->down[1], b[4], nullptr, b[6], nullptr); break;
+    case 4: RB(h->blocks[4], b[6], nullptr, b[2]); break;
+    case 5: RB(h->blocks[5], b[2], nullptr, b[5]); break;            // skip 256@13
+    case 6: RB(h->blocks[6], b[5], nullptr, b[2]); break;
+    case 7: RB(h->blocks[7], b[2], nullptr, b[3]); break;
+    case 8: RB(h->blocks[8], b[3], b[5], b[2]); break;               // cat(x, skip) 512@13 -> 128@13
+    case 9: RB(h->blocks[9], b[2], nullptr, b[6]); break;
+    case 10:
     e = run_pair(h, h->upT[0][0], make_args(h, h->upT[0][0], b[6], nullptr, b[3], nullptr, w.cb, tbr),
                  h->upT[0][1], make_args(h, h->upT[0][1], b[6], nullptr, b[3], nullptr, w.cb, tbr), b_pad, s);   // 128@26
     if (e != hipSuccess) return e;
+    break;
+    case 11:
     h->eps_in_buf7 = false;
     h->upd_fused = false;
     if (use_chains(h, b_pad)) {
@@ -698,8 +707,24 @@ hipError_t run_unet(cld_handle h, const Ws& w, const float* x, int t_idx, int b_
     if (e != hipSuccess) return e;
     RC(h->final_cb, b[3], nullptr, b[7], nullptr);
     }
+    break;
+    default: return hipErrorInvalidValue;
+    }
 #undef RB
 #undef RC
+    return hipSuccess;
+}
+
+// One U-Net evaluation (temporal.py:122-180) on the padded latent `x` [b_pad,52,4]: the 12 spans in a row; leaves the
+// final_conv.0 activations [b_pad,52,64] (or the noise prediction, eps_in_buf7) in w.buf[7].
+hipError_t run_unet(cld_handle h, const Ws& w, const float* x, int t_idx, int b_pad, hipStream_t s) {
+    h->launch_counter = 0;
+    h->eval_counter++;
+    h->eval_alg_flop = h->eval_exec_flop = 0.0;
+    h->eval_launches = 0;
+    set_lds_floor(h->lds_floor);
+    for (int k = 0; k < kSpans; ++k)
+        if (hipError_t e = run_unet_span(h, w, x, t_idx, b_pad, k, s); e != hipSuccess) return e;
     return hipSuccess;
 }
 
@@ -797,6 +822,12 @@ int cld_debug_force_kernel(cld_handle h, int32_t which, int32_t form) {
 int cld_debug_conv5_form(int32_t l_in, int32_t c1, int32_t c2, int32_t c_out, int64_t rows, int32_t forced_form) {
     if (l_in < 1 || c1 < 1 || c2 < 0 || c_out < 1 || rows < 0 || forced_form < 0 || forced_form > 4) return CLD_ERR_ARG;
     return conv5_takes_winograd(l_in, c1, c2, c_out, (long)((rows + 15) / 16 * 16), forced_form) ? CLD_FORM_WINOGRAD : CLD_FORM_DIRECT;
+}
+
+int cld_debug_conv5_items(int32_t l_in, int32_t c_out, int64_t rows, int32_t forced_form) {
+    if ((l_in != 13 && l_in != 26) || (c_out != 64 && c_out != 128 && c_out != 256) || rows < 0 || rows > (1L << 30) || forced_form < 0 || forced_form > 4) return CLD_ERR_ARG;
+    const int forced = forced_form == CLD_FORM_WINOGRAD_WHOLE ? 1 : forced_form == CLD_FORM_WINOGRAD_KSPLIT ? 2 : 0;      // wino_item_form
+    return wino1d_item_form(l_in, c_out, (int)((rows + 15) / 16 * 16), forced);
 }
 
 int cld_profile_enable(cld_handle h, int32_t on) {
@@ -1330,6 +1361,36 @@ int cld_unet_forward_t(cld_handle h, const float* x, const float* cond, const in
     HeadArgs a{};
     head_source(h, w, a); a.w = h->head_w; a.b = h->head_b; a.x = w.xw; a.eps_out = eps; a.B = B; a.b_pad = bp;
     HIPCK(h, launch_head(a, s));
+    return CLD_OK;
+}
+
+int cld_debug_unet_span(cld_handle h, int32_t span, const float* x1, const float* x2, const float* cond, int32_t t_idx,
+                        const int32_t* t_rows, float* y, int32_t B, void* workspace, size_t workspace_bytes, void* stream) {
+    int rc = check_common(h, "cld_debug_unet_span", B, t_rows ? 0 : t_idx, workspace, workspace_bytes);
+    if (rc) return rc;
+    if (span < 0 || span >= kSpans) return fail(h, CLD_ERR_ARG, "cld_debug_unet_span: span must be 0..11");
+    if (!x1 || !cond || !y || (kSpanSkip[span] >= 0) != (x2 != nullptr))
+        return fail(h, CLD_ERR_ARG, "cld_debug_unet_span: null pointer (x2: spans 8 and 11 only, and required there)");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int bp = pad16(B);
+    Ws w = carve(workspace, bp);
+    const bool s22 = h->precision == CLD_PRECISION_F16X2;
+    const long n_in = (long)kSpanL[span] * kSpanC[span];
+    if (span == 0) HIPCK(h, launch_pack_latent(x1, w.xw, B, bp, s));
+    else HIPCK(h, launch_act_pack(x1, w.buf[kSpanIn[span]], B, bp, n_in, s22, s));
+    if (x2) HIPCK(h, launch_act_pack(x2, w.buf[kSpanSkip[span]], B, bp, n_in, s22, s));
+    HIPCK(h, launch_cond_bias(cond, h->wc, h->cbias_b, w.cb, B, bp, NCB, s));
+    if (t_rows) HIPCK(h, launch_add_time_bias(w.cb, h->tb, t_rows, h->cfg.n_timesteps, B, NCB, s));
+    h->launch_counter = 0;
+    set_lds_floor(h->lds_floor);
+    HIPCK(h, run_unet_span(h, w, w.xw, t_rows ? -1 : t_idx, bp, span, s));
+    if (span == kSpans - 1) {
+        HeadArgs a{};
+        head_source(h, w, a); a.w = h->head_w; a.b = h->head_b; a.x = w.xw; a.eps_out = y; a.B = B; a.b_pad = bp;
+        HIPCK(h, launch_head(a, s));
+    } else {
+        HIPCK(h, launch_act_unpack(w.buf[kSpanOut[span]], y, B, (long)kSpanL[span + 1] * kSpanC[span + 1], s22, s));
+    }
     return CLD_OK;
 }
 

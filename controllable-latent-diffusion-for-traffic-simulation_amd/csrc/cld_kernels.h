@@ -91,6 +91,7 @@ bool conv_pair_supported(const ConvGeom& a, const ConvGeom& b);
 // L = 13 (256 -> 256, 128 -> 128, 128 -> 256, cat(256, 256) -> 128); a.wfrag = G g in pack_conv_weights layout with the 8 transform points as taps; exact-fp32 activations only
 bool wino1d_supported(int l_in, int c1, int c2, int c_out);      // c1 | c2: channels of the first | second (concatenated) source
 hipError_t launch_wino1d(const ConvArgs& a, int l_in, int b_pad, int item_form, hipStream_t s);      // item_form: 0 by size; 1 whole items, 2 whole items of eight waves, at every size (tests)
+int wino1d_item_form(int l_in, int c_out, int b_pad, int forced);   // the items a Winograd launch runs: 0 half, 1 whole, 2 whole of eight waves (forced: wino_item_form)
 long wino1d_row_planes(int l_in, int c_out, int b_pad, int item_form);   // (GEMM rows x planes) a launch of that shape and size runs: x 2 C_in C_out = the FLOP its MFMAs execute
 hipError_t launch_wino1d_edge(const ConvArgs& a, int l_in, int b_pad, bool k_split, hipStream_t s);      // wino1d_edge.hip; a.wfrag = the 12-plane fragments; k_split: eight waves per item
 long wino1d_edge_row_planes(int l_in, int b_pad);
@@ -201,6 +202,9 @@ struct HeadArgs {
 hipError_t launch_head(const HeadArgs& a, hipStream_t s);
 // out[b] = mean_{t,d} log N(xq[b]; mean[b], sigma)
 hipError_t launch_logprob(const float* xq, const float* mean, float sigma, float* out, int B, hipStream_t s);
+// a plain [B, n] fp32 tensor into an activation buffer [b_pad, n] (pad rows zero) and back, fp32 or S22 (n % 8 == 0; cld_debug_unet_span)
+hipError_t launch_act_pack(const float* x, float* buf, int B, int b_pad, long n, bool s22, hipStream_t s);
+hipError_t launch_act_unpack(const float* buf, float* x, int B, long n, bool s22, hipStream_t s);
 // copy [B,52,4] rows out of a padded buffer
 hipError_t launch_unpack(const float* xw, float* x, int B, hipStream_t s);
 

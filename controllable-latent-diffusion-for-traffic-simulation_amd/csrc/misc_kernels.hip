@@ -31,6 +31,45 @@ hipError_t launch_pack_latent(const float* x, float* xw, int B, int b_pad, hipSt
     hipLaunchKernelGGL(pack_latent_kernel, dim3((ntot + 255) / 256), dim3(256), 0, s, x, xw, nreal, ntot);
     return hipGetLastError();
 }
+// cld_debug_unet_span: a plain [B, n] fp32 tensor to / from an activation buffer [b_pad, n] (pad rows zero), fp32 or S22 (every
+// 8-channel block of a row as [8 x fp16 hi][8 x fp16 lo], hi = fp16(a), lo = fp16(a - hi): conv_block.hip s22_encode).  One thread per
+// 8-value block; n is a multiple of 8.
+__global__ void act_pack_kernel(const float* __restrict__ x, float* __restrict__ buf, long nreal8, long ntot8, int s22) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= ntot8) return;
+    float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (i < nreal8)
+        for (int e = 0; e < 8; ++e) v[e] = x[i * 8 + e];
+    if (!s22) {
+        for (int e = 0; e < 8; ++e) buf[i * 8 + e] = v[e];
+        return;
+    }
+    _Float16* h = reinterpret_cast<_Float16*>(buf + i * 8);
+    for (int e = 0; e < 8; ++e) {
+        const float c = fminf(fmaxf(v[e], -65504.0f), 65504.0f);
+        const _Float16 hi = (_Float16)c;
+        h[e] = hi;
+        h[8 + e] = (_Float16)(c - (float)hi);
+    }
+}
+__global__ void act_unpack_kernel(const float* __restrict__ buf, float* __restrict__ x, long nreal8, int s22) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nreal8) return;
+    const _Float16* h = reinterpret_cast<const _Float16*>(buf + i * 8);
+    for (int e = 0; e < 8; ++e) x[i * 8 + e] = s22 ? (float)h[e] + (float)h[8 + e] : buf[i * 8 + e];
+}
+hipError_t launch_act_pack(const float* x, float* buf, int B, int b_pad, long n, bool s22, hipStream_t s) {
+    if (n % 8) return hipErrorInvalidValue;
+    const long ntot8 = (long)b_pad * n / 8;
+    hipLaunchKernelGGL(act_pack_kernel, dim3((unsigned)((ntot8 + 255) / 256)), dim3(256), 0, s, x, buf, (long)B * n / 8, ntot8, s22 ? 1 : 0);
+    return hipGetLastError();
+}
+hipError_t launch_act_unpack(const float* buf, float* x, int B, long n, bool s22, hipStream_t s) {
+    if (n % 8) return hipErrorInvalidValue;
+    const long nreal8 = (long)B * n / 8;
+    hipLaunchKernelGGL(act_unpack_kernel, dim3((unsigned)((nreal8 + 255) / 256)), dim3(256), 0, s, buf, x, nreal8, s22 ? 1 : 0);
+    return hipGetLastError();
+}
 hipError_t launch_unpack(const float* xw, float* x, int B, hipStream_t s) {
     return hipMemcpyAsync(x, xw, sizeof(float) * (size_t)B * 52 * 4, hipMemcpyDeviceToDevice, s);
 }

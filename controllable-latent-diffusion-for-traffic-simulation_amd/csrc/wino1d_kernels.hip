@@ -429,6 +429,7 @@ static int item_form_of(int l_in, int c_out, int b_pad, int forced) {
     if (takes_ksplit(l_in, c_out, b_pad)) return 2;
     return takes_halves(l_in, c_out, b_pad) ? 0 : 1;
 }
+int wino1d_item_form(int l_in, int c_out, int b_pad, int forced) { return item_form_of(l_in, c_out, b_pad, forced); }
 long wino1d_row_planes(int l_in, int c_out, int b_pad, int item_form) {
     const int f = item_form_of(l_in, c_out, b_pad, item_form);
     return f == 1 || f == 2 ? wino1d_edge_row_planes(l_in, b_pad) : 8L * wino1d_gemm_rows(l_in, b_pad);

@@ -24,6 +24,9 @@ for _li in range(4):
     CONTEXT_LAYERS += [(3, _s, _hin, _c // _s, _c), (3, 1, _hin // _s, _c, _c), (3, 1, _hin // _s, _c, _c), (3, 1, _hin // _s, _c, _c)]
 CONTEXT_LAYERS += [(1, 2, 56 >> (_li - 1), 32 << _li, 64 << _li) for _li in range(1, 4)]
 
+# the 12 spans of a U-Net evaluation in cld_debug_unet_span's order: (L, C) of each span's input per agent (span 8 / 11: and of its skip);
+# span k's output is span k + 1's input, span 11's the noise prediction [52, 4]
+UNET_SPANS = [(52, 4), (26, 64), (26, 128), (26, 128), (13, 128), (13, 256), (13, 256), (13, 256), (13, 256), (13, 128), (13, 128), (26, 128)]
 
 def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else C.c_void_p(t.data_ptr())
@@ -114,9 +117,34 @@ class Engine:
     def force_kernel(self, which: str, form: str = "auto"):
         """Tests only (cld_debug_force_kernel): run the "guide" / "decode" / "encode" kernel of this engine in its "valu" or
         "mfma" formulation instead of letting the batch size pick ("auto")."""
-        if which not in _lib.KERNELS or form not in _lib.FORMS:
-            raise CldError(f"force_kernel: unknown kernel '{which}' or formulation '{form}'")
-        self._check(self.lib.cld_debug_force_kernel(self._h, _lib.KERNELS[which], _lib.FORMS[form]), "cld_debug_force_kernel")
+        try:
+            fid = _lib.form_id(which, form)
+        except ValueError as ex:
+            raise CldError(f"force_kernel: {ex}") from None
+        self._check(self.lib.cld_debug_force_kernel(self._h, _lib.KERNELS[which], fid), "cld_debug_force_kernel")
+
+    def debug_unet_span(self, span: int, x1, cond, t, x2=None):
+        """Tests only (cld_debug_unet_span): span `span` (0..11) of a U-Net evaluation, the same launches `unet_forward` makes for it
+        in the form `force_kernel("unet" / "conv5", ...)` holds.  x1 [B, L, C] (span 0: the latent [B,52,4]); x2 the skip [B, L, C]
+        of spans 8 (ups.0.0) and 11 (ups.1.*); t one timestep for all rows or a [B] sequence.  Returns [B, L', C'] (span 11: eps [B,52,4])."""
+        if not 0 <= span < len(UNET_SPANS):
+            raise CldError(f"debug_unet_span: span {span} out of range")
+        (L, C), (Lo, Co) = UNET_SPANS[span], (UNET_SPANS + [(52, 4)])[span + 1]
+        B = int(x1.shape[0])
+        x1 = self._f32(x1, (B, L, C))
+        x2 = None if x2 is None else self._f32(x2, (B, L, C))
+        cond = self._f32(cond, (B, 256))
+        t_rows = None
+        if isinstance(t, (int, np.integer)):
+            t_idx = int(t)
+        else:
+            t_rows, t_idx = self._timesteps(t, B), 0
+        y = torch.empty(B, Lo, Co, dtype=torch.float32, device=self.device)
+        ws, nbytes = self._workspace(B)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cld_debug_unet_span(self._h, int(span), _ptr(x1), _ptr(x2), _ptr(cond), t_idx, _ptr(t_rows), _ptr(y), B,
+                                                     ws, nbytes, self._stream()), "cld_debug_unet_span")
+        return y
 
     def debug_context_layer(self, layer: int, x, residual=None, relu: bool = True):
         """Tests only (cld_debug_context_layer): layer `layer` of the ContextEncoder's ResNet-18 on n <= 256 agents, in the form

@@ -421,6 +421,23 @@ int cld_world_step(cld_handle h, const float* traj, const float* centroid, const
  * direct form whatever is forced.  Layers without a Winograd instance always answer CLD_FORM_DIRECT.  < 0: bad argument. */
 int cld_debug_conv5_form(int32_t l_in, int32_t c1, int32_t c2, int32_t c_out, int64_t rows, int32_t forced_form);
 
+/* The items a Winograd F(4, 5) launch of a k5 layer at `l_in` = 13 / 26 rows with `c_out` = 64 / 128 / 256 output channels runs in a launch
+ * set of `rows` agents (padded to 16 inside), with `forced_form` as for cld_debug_conv5_form (no handle, no device call; tests): 0 half
+ * items (wino1d_kernels.hip), 1 whole items (wino1d_edge.hip), 2 whole items of eight waves.  Whether the launch takes Winograd at all is
+ * cld_debug_conv5_form's answer.  < 0: bad argument. */
+int cld_debug_conv5_items(int32_t l_in, int32_t c_out, int64_t rows, int32_t forced_form);
+
+/* One of the 12 spans a U-Net evaluation is run as (tests): the same launches cld_unet_forward makes for that span, in the form
+ * cld_debug_force_kernel(CLD_KERNEL_UNET / CLD_KERNEL_CONV5, ...) holds.  Spans (input -> output per agent, [L, C] row-major):
+ *   0 downs.0.* [52,4] -> [26,64]; 1 downs.1.0 -> [26,128]; 2 downs.1.1 -> [26,128]; 3 downs.1.2 -> [13,128]; 4 downs.2.0 -> [13,256];
+ *   5 downs.2.1, 6 mid_block1, 7 mid_block2 -> [13,256]; 8 ups.0.0 cat(x1, x2 [13,256]) -> [13,128]; 9 ups.0.1 -> [13,128];
+ *   10 ups.0.2 -> [26,128]; 11 ups.1.*, final_conv.* cat(x1, x2 [26,128]) -> eps [52,4].
+ * x1 / x2 / y are DEVICE fp32 [B, L, C]; x2 (the skip) is given for spans 8 and 11 only.  The timestep is t_idx for every row, or
+ * t_rows [B] (DEVICE int32) per row when non-null.  cond [B,256] gives the cond half of the blocks' bias as in cld_unet_forward.  The
+ * entry packs x1 / x2 into the workspace's activation buffers (split fp16 hi / lo planes on CLD_PRECISION_F16X2 handles) and unpacks y. */
+int cld_debug_unet_span(cld_handle h, int32_t span, const float* x1, const float* x2, const float* cond, int32_t t_idx,
+                        const int32_t* t_rows, float* y, int32_t B, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Measurement aid for bench.py (no reference counterpart): while enabled, every launch of the
  * dominant kernel instance -- the Conv1d(k=5) + GroupNorm + Mish block producing 256 channels at
  * L = 13 (conv_block_kernel<13,13,1,5,32,*,*,1,32,1,0,0,0>: 7 launches per U-Net evaluation, all with 256 input

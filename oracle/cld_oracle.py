@@ -144,6 +144,180 @@ def unet_forward(w: Dict[str, Tensor], x: Tensor, cond: Tensor, t: Tensor,
     return h.transpose(1, 2)                                # temporal.py:176
 
 
+# The U-Net as the 12 spans cld_debug_unet_span runs (include/cld.h), [B, L, C] in and out like the debug entry:
+#   0 downs.0.* | 1 downs.1.0 | 2 downs.1.1 | 3 downs.1.2 | 4 downs.2.0 | 5 downs.2.1 | 6 mid_block1 | 7 mid_block2 |
+#   8 ups.0.0 (cat with the skip) | 9 ups.0.1 | 10 ups.0.2 | 11 ups.1.* (cat with the skip), final_conv.* -> eps
+UNET_SPAN_SHAPES = [(52, 4), (26, 64), (26, 128), (26, 128), (13, 128), (13, 256), (13, 256), (13, 256), (13, 256), (13, 128), (13, 128),
+                    (26, 128), (52, 4)]        # (L, C) of span k's input (and skip); entry 12: eps
+UNET_SPAN_SKIP = {8: 5, 11: 2}                 # span -> the span whose output is its skip input
+
+
+def unet_tc(w: Dict[str, Tensor], cond: Tensor, t: Tensor) -> Tensor:
+    """[time_mlp(t) | cond] (temporal.py:141-146), the input of every block's Linear(Mish(.)): [B, 32 + 256] in cond's dtype."""
+    dt = cond.dtype
+    te = sinusoidal_emb(t, w["model.time_mlp.1.weight"].shape[1], dt)
+    te = F.linear(te, w["model.time_mlp.1.weight"].to(dt), w["model.time_mlp.1.bias"].to(dt))
+    te = F.linear(F.mish(te), w["model.time_mlp.3.weight"].to(dt), w["model.time_mlp.3.bias"].to(dt))
+    return torch.cat([te, cond], dim=-1)
+
+
+def _tile_max(r: Tensor) -> Tensor:
+    """r [B, C, L] -> the maximum over each aligned 4-row tile along L (rows 4j..4j+3; a short last tile on its own)."""
+    L = r.shape[-1]
+    L4 = (L + 3) // 4 * 4
+    m = F.pad(r, (0, L4 - L)).reshape(*r.shape[:-1], L4 // 4, 4).amax(-1)
+    return m.repeat_interleave(4, dim=-1)[..., :L]
+
+
+class _Walk:
+    """One span evaluated in `dtype`, optionally with the running-error magnitude R (units of u, fp64) of an fp32 evaluation: linear
+    ops R_y = |W| |x| + sqrt(W^2 R_x^2) + |b| (the layer's own rounding by magnitude, its input's rounding errors in quadrature: the
+    triangle form |W| (|x| + R_x) grows by ~sqrt(K) per layer and buries a 2^-12 weight error after five layers); GroupNorm |g| / sigma (R_y + mean_g R_y + |hat h| mean_g(|hat h| R_y)) + |out|;
+    Mish |mish'| R + |out|; sums R_a + R_b + |sum|.  tile: R of every k5 convolution is its maximum over the aligned 4-row output tile
+    (a Winograd F(4, 5) rounding in the transform domain reaches the whole tile)."""
+
+    def __init__(self, w, dtype, bound: bool, tile: bool):
+        self.w, self.dt, self.bound, self.tile = w, dtype, bound, tile
+
+    def W(self, k):
+        return self.w[k].to(self.dt)
+
+    def conv(self, x, R, key, k5=False, transposed=False, **kw):
+        wt, b = self.W(key + ".weight"), self.W(key + ".bias")
+        op = F.conv_transpose1d if transposed else F.conv1d
+        y = op(x, wt, b, **kw)
+        if not self.bound:
+            return y, None
+        wd = wt.double()
+        Ry = op(x.double().abs(), wd.abs(), b.double().abs(), **kw)
+        if R is not None:
+            Ry = Ry + torch.sqrt(op(R * R, wd * wd, None, **kw))
+        if k5 and self.tile:
+            Ry = _tile_max(Ry)
+        return y, Ry
+
+    def mish(self, x, R):
+        y = F.mish(x)
+        if not self.bound:
+            return y, None
+        xd = x.detach().double().clone().requires_grad_(True)
+        with torch.enable_grad():
+            (g,) = torch.autograd.grad(F.mish(xd).sum(), xd)
+        return y, g.abs() * R + y.double().abs()
+
+    def group_norm(self, y, R, p):
+        g, b = self.W(p + ".weight"), self.W(p + ".bias")
+        out = F.group_norm(y, 8, g, b, eps=1e-5)
+        if not self.bound:
+            return out, None
+        B, C, L = y.shape
+        yg = y.double().reshape(B, 8, -1)
+        mu = yg.mean(-1, keepdim=True)
+        sig = torch.sqrt(yg.var(-1, unbiased=False, keepdim=True) + 1e-5)
+        hh = (yg - mu) / sig
+        Rg = R.reshape(B, 8, -1)
+        e = (Rg + Rg.mean(-1, keepdim=True) + hh.abs() * (hh.abs() * Rg).mean(-1, keepdim=True)) / sig
+        return out, g.double().abs()[None, :, None] * e.reshape(B, C, L) + out.double().abs()
+
+    def add(self, a, Ra, b, Rb):
+        y = a + b
+        return y, (None if not self.bound else Ra + Rb + y.double().abs())
+
+    def conv_block(self, x, R, p):
+        y, R = self.conv(x, R, p + ".block.0", k5=True, padding=2)
+        y, R = self.group_norm(y, R, p + ".block.2")
+        return self.mish(y, R)
+
+    def res_block(self, x, R, tm, Rtm, p):
+        tb, Rtb = self.linear(tm, Rtm, p + ".time_mlp.1")
+        h, Rh = self.conv_block(x, R, p + ".blocks.0")
+        h, Rh = self.add(h, Rh, tb[:, :, None], None if Rtb is None else Rtb[:, :, None])
+        h, Rh = self.conv_block(h, Rh, p + ".blocks.1")
+        if (p + ".residual_conv.weight") in self.w:
+            r, Rr = self.conv(x, R, p + ".residual_conv")
+        else:
+            r, Rr = x, R
+            if self.bound and Rr is None:
+                Rr = torch.zeros_like(x, dtype=torch.float64)
+        return self.add(h, Rh, r, Rr)
+
+    def linear(self, x, R, key):
+        wt, b = self.W(key + ".weight"), self.W(key + ".bias")
+        y = F.linear(x, wt, b)
+        if not self.bound:
+            return y, None
+        wd = wt.double()
+        Ry = F.linear(x.double().abs(), wd.abs(), b.double().abs())
+        return y, Ry if R is None else Ry + torch.sqrt(F.linear(R * R, wd * wd))
+
+
+def unet_tc_bound(w: Dict[str, Tensor], cond: Tensor, t: Tensor):
+    """`unet_tc` in float64 with its running-error magnitude (units of u; _Walk): the time embedding's two Linears and Mish, the
+    sinusoids counted as rounded once; cond as exact -> (tc, R_tc) [B, 288]."""
+    cond = cond.double()
+    wk = _Walk(w, torch.float64, True, False)
+    e = sinusoidal_emb(t, w["model.time_mlp.1.weight"].shape[1], torch.float64)
+    te, R = wk.linear(e, e.abs(), "model.time_mlp.1")
+    te, R = wk.mish(te, R)
+    te, R = wk.linear(te, R, "model.time_mlp.3")
+    return torch.cat([te, cond], dim=-1), torch.cat([R, torch.zeros_like(cond)], dim=-1)
+
+
+def _unet_span(w, k: int, x1: Tensor, x2: Optional[Tensor], tc: Tensor, bound: bool, tile: bool, Rtc: Optional[Tensor] = None):
+    if (x2 is not None) != (k in UNET_SPAN_SKIP):
+        raise ValueError(f"span {k}: the skip input is given for spans {sorted(UNET_SPAN_SKIP)} only, and required there")
+    dt = x1.dtype
+    wk = _Walk(w, dt, bound, tile)
+    h = x1.to(dt).transpose(1, 2)
+    if x2 is not None:
+        h = torch.cat((h, x2.to(dt).transpose(1, 2)), dim=1)          # temporal.py:164
+    R = None
+    if bound and Rtc is None:
+        Rtc = torch.zeros_like(tc, dtype=torch.float64)
+    tm, Rtm = wk.mish(tc.to(dt), Rtc)
+    names = {1: "downs.1.0", 2: "downs.1.1", 4: "downs.2.0", 5: "downs.2.1", 6: "mid_block1", 7: "mid_block2", 8: "ups.0.0", 9: "ups.0.1"}
+    if k == 0:
+        h, R = wk.res_block(h, R, tm, Rtm, "model.downs.0.0")
+        h, R = wk.res_block(h, R, tm, Rtm, "model.downs.0.1")
+        h, R = wk.conv(h, R, "model.downs.0.2.conv", stride=2, padding=1)
+    elif k in names:
+        h, R = wk.res_block(h, R, tm, Rtm, "model." + names[k])
+    elif k == 3:
+        h, R = wk.conv(h, R, "model.downs.1.2.conv", stride=2, padding=1)
+    elif k == 10:
+        h, R = wk.conv(h, R, "model.ups.0.2.conv", transposed=True, stride=2, padding=1)
+    elif k == 11:
+        h, R = wk.res_block(h, R, tm, Rtm, "model.ups.1.0")
+        h, R = wk.res_block(h, R, tm, Rtm, "model.ups.1.1")
+        h, R = wk.conv(h, R, "model.ups.1.2.conv", transposed=True, stride=2, padding=1)
+        h, R = wk.conv_block(h, R, "model.final_conv.0")
+        h, R = wk.conv(h, R, "model.final_conv.1")
+    else:
+        raise ValueError(f"span {k} out of range 0..11")
+    y = h.transpose(1, 2)
+    if not bound:
+        return y
+    if tile:
+        R = _tile_max(R)
+    return y, R.transpose(1, 2)
+
+
+def unet_span(w: Dict[str, Tensor], k: int, x1: Tensor, x2: Optional[Tensor], tc: Tensor) -> Tensor:
+    """Span k of `unet_forward` (UNET_SPAN_SHAPES) in x1's dtype: x1 [B, L, C] (span 0: the latent [B,52,4]), x2 the skip [B, L, C]
+    of spans 8 and 11 (None otherwise), tc = unet_tc(w, cond, t) -> [B, L', C'] (span 11: eps [B,52,4])."""
+    return _unet_span(w, k, x1, x2, tc, False, False)
+
+
+def unet_span_bound(w: Dict[str, Tensor], k: int, x1: Tensor, x2: Optional[Tensor], tc: Tensor, tile: bool = False,
+                    Rtc: Optional[Tensor] = None):
+    """`unet_span` with the running-error magnitude R of an fp32 evaluation of the span (class _Walk), in x1's dtype (fp64 for a
+    reference) -> (y, R), R in units of u = 2^-24 per output element: an fp32 evaluation keeps |y32 - y| <= kappa u R for a kappa of
+    order one (a model of the error rather than a strict bound: input errors add in quadrature).  The inputs count as exact, tc up to
+    Rtc (unet_tc_bound; default exact).  tile=True: a form that runs the span's k5 convolutions as Winograd F(4, 5)
+    (R over each aligned 4-row tile of every k5 output and of the span's output)."""
+    return _unet_span(w, k, x1, x2, tc, True, tile, Rtc)
+
+
 # --------------------------------------------------------------------------- #
 # a-3 / a-2 / a-8  DDPM update, sampling loop, log-prob
 # --------------------------------------------------------------------------- #

@@ -214,6 +214,27 @@ def test_force_kernel_tables_match_header():
     assert set(_lib.FORMS) == set(forms)
     for name, macro in forms.items():
         assert _lib.FORMS[name] == defs["CLD_FORM_" + macro], name
+    # per kernel: every (kernel, name) pair -> its macro, and the names a kernel does not have are refused (the numbers are reused across
+    # kernels: "winograd_f2" given for the k5 layers would silently run whole items)
+    per_kernel = {"guide": {"auto": "AUTO", "valu": "VALU", "mfma": "MFMA", "quad": "MFMA_QUAD"},
+                  "decode": {"auto": "AUTO", "valu": "VALU", "mfma": "MFMA"}, "encode": {"auto": "AUTO", "valu": "VALU", "mfma": "MFMA"},
+                  "unet": {"auto": "AUTO", "layers": "LAYERS", "chain": "CHAIN", "chain1": "CHAIN_TILE1", "chain4": "CHAIN_TILE4",
+                           "chainw": "CHAIN_WINO", "chainw2": "CHAIN_WINO2", "chainw1": "CHAIN_WINO1"},
+                  "context": {"auto": "AUTO", "direct": "DIRECT", "winograd": "WINOGRAD", "winograd_f2": "WINOGRAD_F2"},
+                  "conv5": {"auto": "AUTO", "direct": "DIRECT", "winograd": "WINOGRAD", "winograd_whole": "WINOGRAD_WHOLE",
+                            "winograd_ksplit": "WINOGRAD_KSPLIT"}}
+    assert set(_lib.KERNEL_FORMS) == set(per_kernel)
+    for kind, names in per_kernel.items():
+        assert set(_lib.KERNEL_FORMS[kind]) == set(names), kind
+        for name, macro in names.items():
+            assert _lib.form_id(kind, name) == defs["CLD_FORM_" + macro], (kind, name)
+        for name in set(forms) - set(names):
+            with pytest.raises(ValueError):
+                _lib.form_id(kind, name)
+    with pytest.raises(ValueError):
+        _lib.form_id("conv5", "winograd_f2")
+    with pytest.raises(ValueError):
+        _lib.form_id("nope", "auto")
 
 
 def test_conv5_form_rule_and_its_32_bit_fallback():
@@ -424,3 +445,106 @@ def test_context_pass_size():
         assert 128 <= p <= 256, B
         total = lambda q: (B // q) * cost(q) + (cost(B % q) if B % q else 0)      # noqa: E731
         assert total(p) == min(total(q) for q in range(128, 257)), B
+
+
+def test_conv5_item_forms_per_winograd_shape():
+    """The items a Winograd launch runs (cld_debug_conv5_items; wino1d_kernels.hip item_form_of), pinned for each of the 7
+    CLD_WINO1D_INSTANCES shapes.  nfull = padded rows / (16 at L = 13, 8 at L = 26) x c_out / 64 items: eight-wave whole items (2) for
+    192 <= nfull <= 256, half items (0) below 512 and when the last generation of 512 is at most half full, whole items (1) otherwise;
+    a forced form overrides the size."""
+    from cld_amd import _lib
+    f = _lib.load().cld_debug_conv5_items
+    AUTO, WHOLE, KSPLIT, WINO = (_lib.form_id("conv5", n) for n in ("auto", "winograd_whole", "winograd_ksplit", "winograd"))
+    for (l, c1, c2, co) in [(13, 256, 0, 256), (13, 128, 0, 128), (13, 128, 0, 256), (13, 256, 256, 128), (26, 128, 0, 128),
+                            (26, 64, 0, 128), (26, 128, 128, 64)]:
+        ag, ncb = (16 if l == 13 else 8), co // 64          # agents per item group, items per group
+
+        def model(nfull):
+            if 192 <= nfull <= 256:
+                return 2
+            return 0 if nfull < 512 or 0 < nfull % 512 <= 256 else 1
+        for groups in range(1, 1100):
+            bp = (groups * ag + 15) // 16 * 16
+            assert f(l, co, groups * ag, AUTO) == model(bp // ag * ncb), (l, co, groups)
+        assert f(l, co, 1024 // ncb * ag - 15, AUTO) == 1 and model(1024) == 1          # rows pad to 16 inside
+        assert model(191) == 0 and model(257) == 0 and model(768) == 0 and model(769) == 1 and model(512) == 1
+
+        def rows(nfull):
+            return nfull // ncb * ag
+        for n in (1, rows(100), rows(200), rows(600)):
+            assert f(l, co, n, WHOLE) == 1 and f(l, co, n, KSPLIT) == 2
+            assert f(l, co, n, WINO) == f(l, co, n, AUTO)
+    assert f(52, 64, 4096, AUTO) < 0 and f(13, 96, 4096, AUTO) < 0 and f(13, 256, -1, AUTO) < 0 and f(13, 256, 64, 5) < 0
+
+
+def test_unet_spans_compose_to_the_oracle_unet():
+    """oracle.unet_span 0..11 chained (skips from spans 5 and 2) equal unet_forward: bit for bit in float64 with one timestep, and in
+    float32 with per-row timesteps."""
+    import torch
+    from cld_amd import synth
+    from oracle import cld_oracle as O
+    w = O.to_torch(synth.make_unet_weights(0, affine_jitter=True))
+    g = torch.Generator().manual_seed(5)
+    B = 6
+    x = torch.randn(B, 52, 4, generator=g) * 3
+    cond = torch.randn(B, 256, generator=g)
+    for dt, t in ((torch.float64, torch.full((B,), 42)), (torch.float32, torch.randint(0, 100, (B,), generator=g))):
+        wd = {k: v.to(dt) for k, v in w.items()}
+        ref = O.unet_forward(wd, x.to(dt), cond.to(dt), t)
+        tc = O.unet_tc(wd, cond.to(dt), t)
+        outs, h = [], x.to(dt)
+        for k in range(12):
+            assert tuple(h.shape[1:]) == O.UNET_SPAN_SHAPES[k]
+            h = O.unet_span(wd, k, h, outs[O.UNET_SPAN_SKIP[k]] if k in O.UNET_SPAN_SKIP else None, tc)
+            outs.append(h)
+        assert torch.equal(h, ref), dt
+
+
+def test_unet_span_bound_holds_for_fp32_and_sees_a_wrong_tap():
+    """The float32 oracle's own spans stay within kappa u R of the float64 reference (oracle.unet_span_bound) with kappa = 8, element by
+    element, on real and x64-edge inputs, with and without the Winograd tile maximum -- the R formula is checked before any GPU number.
+    And R is tight enough to see a subtle fault on real inputs: tap 0 of any one k5 layer of a span scaled by 1 + 2^-12 lands more than
+    10x above twice the largest fp32 ratio, in every span, the five-layer spans 0 and 11 (the chain head and tail) included."""
+    import torch
+    from cld_amd import synth
+    from oracle import cld_oracle as O
+    w64 = O.to_torch(synth.make_unet_weights(0, affine_jitter=True), dtype=torch.float64)
+    w32 = {k: v.float() for k, v in w64.items()}
+    g = torch.Generator().manual_seed(9)
+    B = 8
+    cond = torch.randn(B, 256, generator=g, dtype=torch.float64)
+    t = torch.randint(0, 100, (B,), generator=g)
+    tc, Rtc = O.unet_tc_bound(w64, cond, t)
+    tc32 = O.unet_tc(w32, cond.float(), t)
+    h = (torch.randn(B, 52, 4, generator=g, dtype=torch.float64) * 3).float().double()
+    outs = []
+    U = 2.0 ** -24
+    for k in range(12):
+        skip = outs[O.UNET_SPAN_SKIP[k]] if k in O.UNET_SPAN_SKIP else None
+        for edge in (False, True):
+            s = torch.ones(h.shape[1], dtype=torch.float64)
+            if edge:
+                s[[r for r in (0, 3, 4, 7, 8, 11, 12, h.shape[1] - 1) if r < h.shape[1]]] = 64.0
+            x1 = h * s[None, :, None]
+            x2 = None if skip is None else skip * (s[None, :, None] if skip.shape[1] == h.shape[1] else 1.0)
+            y32 = O.unet_span(w32, k, x1.float(), None if x2 is None else x2.float(), tc32).double()
+            for tile in (False, True):
+                y64, R = O.unet_span_bound(w64, k, x1, x2, tc, tile=tile, Rtc=Rtc)
+                assert ((y32 - y64).abs() <= 8 * U * R).all(), (k, edge, tile)
+        y64, R = O.unet_span_bound(w64, k, h, skip, tc, Rtc=Rtc)
+        y32 = O.unet_span(w32, k, h.float(), None if skip is None else skip.float(), tc32).double()
+        normal = float(((y32 - y64).abs() / (U * R)).max())
+        prefix = {0: ("model.downs.0.",), 11: ("model.ups.1.", "model.final_conv."), 1: ("model.downs.1.0.",), 2: ("model.downs.1.1.",),
+                  4: ("model.downs.2.0.",), 5: ("model.downs.2.1.",), 6: ("model.mid_block1.",), 7: ("model.mid_block2.",),
+                  8: ("model.ups.0.0.",), 9: ("model.ups.0.1.",)}.get(k, ())
+        layers = [key for key in w64 if key.endswith(".block.0.weight") and key.startswith(prefix)] if prefix else []
+        assert len(layers) == {0: 4, 11: 5}.get(k, 2 if prefix else 0), (k, layers)
+        for key in layers:
+            wf = dict(w64)
+            wt = wf[key].clone()
+            wt[..., 0] *= 1 + 2.0 ** -12
+            wf[key] = wt
+            yf = O.unet_span(wf, k, h, skip, tc)
+            assert float(((yf - y64).abs() / (U * R)).max()) > 10 * 2 * normal, (k, key)
+        outs.append(y64.float().double())
+        h = outs[-1]
