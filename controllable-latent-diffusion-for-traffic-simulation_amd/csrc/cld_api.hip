@@ -12,6 +12,7 @@
 
 #include "../../include/cld.h"
 #include "cld_kernels.h"
+#include "train.h"
 
 using namespace cld;
 
@@ -1971,6 +1972,62 @@ int cld_world_step(cld_handle h, const float* traj, const float* centroid, const
     if (!h) return CLD_ERR_ARG;
     if (!traj || !centroid || !yaw || !world || B < 1 || k < 0 || k >= T) return fail(h, CLD_ERR_ARG, "cld_world_step: bad argument");
     HIPCK(h, launch_world_step(traj, centroid, yaw, k, world, next_curr_states, B, static_cast<hipStream_t>(stream)));
+    return CLD_OK;
+}
+
+/* ---- U-Net training (train_kernels.hip) ---- */
+int cld_unet_param_count(cld_handle) { return kTrainParams; }
+
+int cld_unet_param_info(cld_handle h, int32_t i, const char** name, size_t* offset, size_t* numel, int32_t* shape, int32_t* ndim) {
+    if (i < 0 || i >= kTrainParams) return fail(h, CLD_ERR_ARG, "cld_unet_param_info: index out of range");
+    const TrainParam& p = train_params()[i];
+    if (name) *name = p.name;
+    if (offset) *offset = p.offset;
+    if (numel) *numel = p.numel;
+    if (ndim) *ndim = p.ndim;
+    if (shape)
+        for (int d = 0; d < 3; ++d) shape[d] = d < p.ndim ? p.shape[d] : 1;
+    return CLD_OK;
+}
+
+size_t cld_unet_param_floats(cld_handle) { return train_param_floats(); }
+
+size_t cld_unet_tape_bytes(cld_handle, int32_t B) { return B < 1 ? 0 : train_tape_floats(B) * sizeof(float); }
+
+size_t cld_unet_train_workspace_bytes(cld_handle, int32_t B) { return B < 1 ? 0 : train_ws_floats(B) * sizeof(float); }
+
+static int check_train(cld_handle h, const char* fn, int B, const void* tape, size_t tape_bytes, const void* ws, size_t ws_bytes) {
+    if (!h) return CLD_ERR_ARG;
+    if (h->precision != CLD_PRECISION_F32)
+        return fail(h, CLD_ERR_STATE, std::string(fn) + ": training runs in exact fp32 only (this handle is CLD_PRECISION_F16X2)");
+    if (!h->finalized || !h->has_unet) return fail(h, CLD_ERR_STATE, std::string(fn) + ": the handle has no finalized U-Net weights (model.*)");
+    if (B < 1 || B > (1 << 20)) return fail(h, CLD_ERR_ARG, std::string(fn) + ": B out of range [1, 2^20]");
+    if (!tape || tape_bytes < cld_unet_tape_bytes(h, B)) return fail(h, CLD_ERR_WORKSPACE, std::string(fn) + ": tape too small");
+    if (!ws || ws_bytes < cld_unet_train_workspace_bytes(h, B)) return fail(h, CLD_ERR_WORKSPACE, std::string(fn) + ": workspace too small");
+    if (reinterpret_cast<uintptr_t>(ws) % 16 || reinterpret_cast<uintptr_t>(tape) % 16)
+        return fail(h, CLD_ERR_ARG, std::string(fn) + ": workspace and tape must be 16-byte aligned");
+    return CLD_OK;
+}
+
+int cld_unet_train_forward(cld_handle h, const float* params, const float* x, const float* cond, const int32_t* t_idx, float* eps,
+                           float* tape, size_t tape_bytes, int32_t B, void* workspace, size_t workspace_bytes, void* stream) {
+    int rc = check_train(h, "cld_unet_train_forward", B, tape, tape_bytes, workspace, workspace_bytes);
+    if (rc) return rc;
+    if (!params || !x || !cond || !t_idx || !eps) return fail(h, CLD_ERR_ARG, "cld_unet_train_forward: null pointer");
+    HIPCK(h, train_forward(params, x, cond, t_idx, eps, tape, B, static_cast<float*>(workspace), static_cast<hipStream_t>(stream)));
+    return CLD_OK;
+}
+
+int cld_unet_backward(cld_handle h, const float* params, const float* x, const float* cond, const int32_t* t_idx, const float* tape,
+                      size_t tape_bytes, const float* d_eps, float* d_params, float* dx, float* dcond, int32_t accumulate, int32_t B,
+                      void* workspace, size_t workspace_bytes, void* stream) {
+    int rc = check_train(h, "cld_unet_backward", B, tape, tape_bytes, workspace, workspace_bytes);
+    if (rc) return rc;
+    (void)cond; (void)t_idx;      // their contribution is on the tape (tc = [time_mlp(t) | cond])
+    if (!params || !x || !d_eps) return fail(h, CLD_ERR_ARG, "cld_unet_backward: null pointer");
+    if (accumulate != 0 && accumulate != 1) return fail(h, CLD_ERR_ARG, "cld_unet_backward: accumulate must be 0 or 1");
+    HIPCK(h, train_backward(params, x, tape, d_eps, d_params, dx, dcond, accumulate, B, static_cast<float*>(workspace),
+                            static_cast<hipStream_t>(stream)));
     return CLD_OK;
 }
 

@@ -32,6 +32,20 @@ def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+def unet_param_table(lib=None, h=None):
+    """cld_unet_param_info for all 148 U-Net tensors: ([(name, offset, numel, shape)], flat buffer length in floats).  The table is
+    fixed by the architecture; it needs no handle and no device."""
+    lib = lib or _lib.load()
+    out = []
+    name, off, numel = C.c_char_p(), C.c_size_t(), C.c_size_t()
+    shape, ndim = (C.c_int32 * 3)(), C.c_int32()
+    for i in range(int(lib.cld_unet_param_count(h))):
+        _lib.check(h, lib.cld_unet_param_info(h, i, C.byref(name), C.byref(off), C.byref(numel), shape, C.byref(ndim)),
+                   "cld_unet_param_info")
+        out.append((name.value.decode(), int(off.value), int(numel.value), tuple(int(shape[d]) for d in range(ndim.value))))
+    return out, int(lib.cld_unet_param_floats(h))
+
+
 class Engine:
     """Owns a `cld_handle`.  Weights come in under the reference's state_dict names."""
 
@@ -586,6 +600,49 @@ class Engine:
             if want_grad:
                 out["grad"] = gr
         return out
+
+    # ------------------------------------------------------------------ training (exact fp32; cld_unet_train_forward / cld_unet_backward)
+    def unet_param_table(self):
+        """[(name, offset, numel, shape)] of the 148 U-Net tensors in the flat parameter buffer, and the buffer's length in floats."""
+        return unet_param_table(self.lib, self._h)
+
+    def _train_workspace(self, B: int):
+        need = int(self.lib.cld_unet_train_workspace_bytes(self._h, B))
+        if getattr(self, "_tws", None) is None or self._tws.numel() < need:
+            self._tws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return C.c_void_p(self._tws.data_ptr()), C.c_size_t(self._tws.numel())
+
+    def unet_train_forward(self, params, x, cond, t):
+        """eps [B,52,4] of the U-Net with the weights of `params` (flat fp32 device buffer, `unet_param_table` layout) and one
+        timestep per row, plus the tape `unet_backward` needs (a uint8 device tensor)."""
+        x = self._f32(x)
+        B = x.shape[0]
+        x = self._f32(x, (B, T, D)); cond = self._f32(cond, (B, COND))
+        t = self._timesteps(t, B)
+        eps = torch.empty_like(x)
+        tape = torch.empty(int(self.lib.cld_unet_tape_bytes(self._h, B)), dtype=torch.uint8, device=self.device)
+        ws, wsn = self._train_workspace(B)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cld_unet_train_forward(self._h, _ptr(params), _ptr(x), _ptr(cond), _ptr(t), _ptr(eps), _ptr(tape),
+                                                        tape.numel(), B, ws, wsn, self._stream()), "cld_unet_train_forward")
+        return eps, tape
+
+    def unet_backward(self, params, x, cond, t, tape, d_eps, d_params=None, want_dx=True, want_dcond=False, accumulate=False):
+        """Gradients of the U-Net for the cotangent d_eps [B,52,4] from the tape of `unet_train_forward` on the same params / x /
+        cond / t.  d_params: flat fp32 device buffer that receives (accumulate=False) or adds (True) the parameter gradients, or
+        None.  Returns (dx [B,52,4] or None, dcond [B,256] or None)."""
+        x = self._f32(x)
+        B = x.shape[0]
+        x = self._f32(x, (B, T, D)); cond = self._f32(cond, (B, COND)); d_eps = self._f32(d_eps, (B, T, D))
+        t = self._timesteps(t, B)
+        dx = torch.empty_like(x) if want_dx else None
+        dcond = torch.empty_like(cond) if want_dcond else None
+        ws, wsn = self._train_workspace(B)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cld_unet_backward(self._h, _ptr(params), _ptr(x), _ptr(cond), _ptr(t), _ptr(tape), tape.numel(),
+                                                   _ptr(d_eps), _ptr(d_params), _ptr(dx), _ptr(dcond), int(bool(accumulate)), B,
+                                                   ws, wsn, self._stream()), "cld_unet_backward")
+        return dx, dcond
 
     def log_prob(self, x_t, x_tm1, cond, t_idx: int):
         x_t = self._f32(x_t)

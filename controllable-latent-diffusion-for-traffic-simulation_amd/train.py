@@ -1,0 +1,175 @@
+"""Training surface of the denoiser: the U-Net's forward and backward on the HIP training path (include/cld.h,
+cld_unet_train_forward / cld_unet_backward) behind torch autograd.
+
+The reference trains `self.dm.parameters()` with Adam in two loops (src/trainers/dm_trainer.py:72-80 on
+`DmModel.compute_losses`, and src/trainers/guide_dm_trainer.py:127-183 `ppo_update` on `DmModel.log_prob` at t = 0).
+`TrainableDm` keeps the U-Net weights in ONE flat fp32 device tensor, exposed as `nn.Parameter` views under the reference's
+state_dict names, so `torch.optim.Adam(dm.parameters())` updates them in place and the next forward reads the new values with no
+host round trip.  The small loss heads (q_sample, MSE, the Normal log-density) are torch elementwise code around the U-Net.
+Exact fp32 only: a "f16x2" engine refuses these calls.
+"""
+from __future__ import annotations
+
+import math
+from typing import Mapping, Optional
+
+import torch
+
+from ._lib import CldError
+from .dm_model import DmModel
+from .engine import Engine, unet_param_table
+
+
+class UnetFn(torch.autograd.Function):
+    """eps = U-Net(x, cond, t) with the weights of `flat`; `params` are the views of `flat` that receive the gradients."""
+
+    @staticmethod
+    def forward(ctx, x, cond, t, engine: Engine, flat, table, *params):
+        eps, tape = engine.unet_train_forward(flat, x, cond, t)
+        ctx.engine, ctx.table, ctx.flat = engine, table, flat
+        ctx.save_for_backward(x.detach(), cond.detach(), torch.as_tensor(t))
+        ctx.tape = tape
+        return eps
+
+    @staticmethod
+    def backward(ctx, d_eps):
+        x, cond, t = ctx.saved_tensors
+        want_dx, want_dcond = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        want_dp = any(ctx.needs_input_grad[6:])
+        d_flat = torch.zeros_like(ctx.flat) if want_dp else None
+        dx, dcond = ctx.engine.unet_backward(ctx.flat, x, cond, t, ctx.tape, d_eps.contiguous(), d_params=d_flat,
+                                             want_dx=want_dx, want_dcond=want_dcond)
+        ctx.tape = None
+        grads = [None] * len(ctx.table)
+        if want_dp:
+            grads = [d_flat[off:off + n].view(shape) for (_, off, n, shape) in ctx.table]
+        return (dx, dcond, None, None, None, None, *grads)
+
+
+def _strip(k: str) -> str:
+    return k[3:] if k.startswith("dm.") else k
+
+
+class _UnetModel:
+    """`dm.model(x, aux_info, t)` (TemporalMapUnet.forward, temporal.py:122-180), differentiable."""
+
+    def __init__(self, dm: "TrainableDm"):
+        self._dm = dm
+
+    def __call__(self, x, aux_info, time):
+        return self._dm._unet(x, aux_info["cond_feat"], time)
+
+
+class TrainableDm:
+    """A trainable DmModel (models/dm/dm_model.py:15-174) over the HIP training path.
+
+    `weights`: the U-Net state_dict ("model.*" keys, optional "dm." prefix).  `parameters()` / `named_parameters()` /
+    `state_dict()` / `load_state_dict()` follow the reference names; `model(x, aux_info, t)`, `compute_losses(aux_info, z0,
+    t=None, noise=None)` and `log_prob(x_t, x_tm1, aux_info, t)` are differentiable with respect to the parameters (and to x /
+    cond where those require grad).  `to_engine()` gives a finalized DmModel with the current weights for sampling."""
+
+    def __init__(self, weights: Mapping, n_timesteps: int = 100, device="cuda:0"):
+        self.n_timesteps = int(n_timesteps)
+        self.device = torch.device(device)
+        self.engine = Engine(n_timesteps=self.n_timesteps, device=device)
+        sd = {_strip(k): v for k, v in weights.items() if _strip(k).startswith("model.")}
+        self.engine.load_state_dict(sd).finalize()     # the training calls need a finalized exact-fp32 U-Net handle
+        self._table, nflat = self.engine.unet_param_table()
+        self._flat = torch.zeros(nflat, dtype=torch.float32, device=self.device)
+        self._params = {}
+        for name, off, n, shape in self._table:
+            p = torch.nn.Parameter(self._flat[off:off + n].view(shape))
+            self._params[name] = p
+        self.load_state_dict(sd)
+        self.model = _UnetModel(self)
+        f = lambda a: torch.from_numpy(a).to(self.device)       # noqa: E731
+        self.x_t_cof, self.noise_cof = f(self.engine.x_t_cof), f(self.engine.noise_cof)
+        self.posterior_log_variance_clipped = f(self.engine.posterior_log_variance_clipped)
+
+    # ------------------------------------------------------------------ parameters
+    @property
+    def flat(self) -> torch.Tensor:
+        """The flat fp32 device buffer the parameters are views of (cld_unet_param_info layout)."""
+        return self._flat
+
+    def named_parameters(self):
+        return iter(self._params.items())
+
+    def parameters(self):
+        return iter(self._params.values())
+
+    def state_dict(self) -> dict:
+        return {k: p.detach().clone() for k, p in self._params.items()}
+
+    def load_state_dict(self, sd: Mapping, strict: bool = True):
+        sd = {_strip(k): v for k, v in sd.items()}
+        missing = [k for k in self._params if k not in sd]
+        unknown = [k for k in sd if k not in self._params and k.startswith("model.")]
+        if strict and (missing or unknown):
+            raise CldError(f"load_state_dict: missing {missing[:4]}, unknown {unknown[:4]}")
+        with torch.no_grad():
+            for k, p in self._params.items():
+                if k in sd:
+                    v = torch.as_tensor(sd[k]).to(device=self.device, dtype=torch.float32)
+                    if tuple(v.shape) != tuple(p.shape):
+                        raise CldError(f"load_state_dict: '{k}' expects shape {tuple(p.shape)}, got {tuple(v.shape)}")
+                    p.copy_(v)
+        return self
+
+    def zero_grad(self, set_to_none: bool = True):
+        for p in self._params.values():
+            if set_to_none:
+                p.grad = None
+            elif p.grad is not None:
+                p.grad.zero_()
+
+    # ------------------------------------------------------------------ the U-Net and the loss heads
+    def _timesteps(self, t, B: int) -> torch.Tensor:
+        t = torch.as_tensor(t, device=self.device).reshape(-1).long()
+        if t.numel() == 1 and B != 1:
+            t = t.expand(B)
+        if t.numel() != B:
+            raise CldError(f"expected {B} timesteps, got {t.numel()}")
+        return t
+
+    def _unet(self, x, cond, t):
+        B = x.shape[0]
+        t = self._timesteps(t, B)
+        return UnetFn.apply(x.float(), cond.float(), t, self.engine, self._flat, self._table, *self._params.values())
+
+    def compute_losses(self, aux_info, z0, t=None, noise=None):
+        """dm_model.py:82-89: F.mse_loss(noise, U-Net(q_sample(z0, t, noise), cond, t)); `t` / `noise` default to the reference's
+        draws (torch.randint / randn_like on the device).  q_sample runs without autograd (z0 gets no gradient: in the reference it
+        is the frozen VAE's latent)."""
+        B = len(z0)
+        if t is None:
+            t = torch.randint(0, self.n_timesteps, (B,), device=self.device)
+        if noise is None:
+            noise = torch.randn(B, 52, 4, device=self.device)
+        t = self._timesteps(t, B)
+        noise = torch.as_tensor(noise).to(self.device, torch.float32)
+        z_noisy = self.engine.q_sample(z0, noise, t)
+        eps = self._unet(z_noisy, aux_info["cond_feat"], t)
+        return torch.nn.functional.mse_loss(noise, eps)
+
+    def log_prob(self, x_t, x_t_minus_1, aux_info, t):
+        """dm_model.py:165-174: log N(x_{t-1}; x_t_cof[t] x_t - noise_cof[t] eps, sigma_t) averaged over (T, D), per row.
+        At t = 0 sigma_0 = exp(0.5 log 1e-20) = 1e-10: see INTEGRATION.md "Training" for what the gradient is there."""
+        x_t = torch.as_tensor(x_t).to(self.device, torch.float32)
+        x_tm1 = torch.as_tensor(x_t_minus_1).to(self.device, torch.float32)
+        B = x_t.shape[0]
+        t = self._timesteps(t, B)
+        eps = self._unet(x_t, aux_info["cond_feat"], t)
+        mean = self.x_t_cof[t].view(-1, 1, 1) * x_t - self.noise_cof[t].view(-1, 1, 1) * eps
+        sigma = (0.5 * self.posterior_log_variance_clipped[t].view(-1, 1, 1)).exp()
+        lp = -((x_tm1 - mean) ** 2) / (2 * sigma ** 2) - sigma.log() - math.log(math.sqrt(2 * math.pi))
+        return lp.mean(dim=(1, 2))
+
+    # ------------------------------------------------------------------ sampling with the current weights
+    def to_engine(self, n_timesteps: Optional[int] = None, precision: str = "f32") -> DmModel:
+        """A finalized DmModel (its own Engine, `n_timesteps` defaulting to this model's) holding the current weights, for the
+        sampling path.  Call it again after optimiser steps: a finalized handle keeps the weights it was given."""
+        n = self.n_timesteps if n_timesteps is None else int(n_timesteps)
+        eng = Engine(n_timesteps=n, device=self.device, precision=precision)
+        eng.load_state_dict(self.state_dict()).finalize()
+        return DmModel(n_timesteps=n, device=self.device, engine=eng)

@@ -520,6 +520,42 @@ int cld_debug_context_layer(cld_handle h, int32_t layer, const float* x, const f
  * size in [128, 256] -- passes of that size and a last one of the rest.  The direct form runs passes of 256.  < 0: bad argument. */
 int cld_debug_context_pass_size(int32_t B);
 
+/* ---- Training (exact fp32).  The reference optimises self.dm.parameters() with Adam in two loops: dm_trainer.py:72-80
+ * (loss = self.dm.compute_losses(aux_info, z0), dm_model.py:82-89, then backward) and guide_dm_trainer.py:127-183 (ppo_update:
+ * self.dm.log_prob(x1, x0, ...) at t = 0, manual_backward(loss), opt.step()).  These calls give the U-Net's half of both: a forward
+ * from weights held in a DEVICE buffer (so an optimiser step needs no host round trip and no cld_finalize) that keeps a tape, and its
+ * backward.  The optimiser stays the caller's.  A CLD_PRECISION_F16X2 handle, or one without finalized U-Net weights, refuses the
+ * compute calls with CLD_ERR_STATE; the table and size queries need no handle (h may be NULL).
+ *
+ * Parameter table: the 148 U-Net tensors of the reference state_dict (temporal.py:48-120), in its order, each at an offset (in floats)
+ * into one flat fp32 buffer, offsets multiples of 64 floats; the floats between tensors are never read or written.  Layouts as in the
+ * reference: Conv1d [C_out,C_in,k], ConvTranspose1d [C_in,C_out,k], Linear [out,in].  `shape` gets 3 entries (1 past ndim). */
+int cld_unet_param_count(cld_handle h);                  /* 148 */
+int cld_unet_param_info(cld_handle h, int32_t i, const char** name, size_t* offset, size_t* numel, int32_t* shape, int32_t* ndim);
+size_t cld_unet_param_floats(cld_handle h);              /* length of the flat buffer (> 4,349,284 values: alignment) */
+/* Tape and workspace bytes of the two calls below for B rows (the workspace covers both). */
+size_t cld_unet_tape_bytes(cld_handle h, int32_t B);
+size_t cld_unet_train_workspace_bytes(cld_handle h, int32_t B);
+
+/* eps = TemporalMapUnet.forward(x, {'cond_feat': cond}, t) (temporal.py:122-180) from the weights in `params` (DEVICE, the flat layout
+ * above), one timestep per row (t_idx [B] DEVICE int32, dm_model.py:84).  x, eps [B,52,4], cond [B,256].  Writes the tape (DEVICE,
+ * caller-owned, >= cld_unet_tape_bytes): the time MLP's activations, tc = [time_mlp(t) | cond], Mish(tc), and per residual block the
+ * pre-GroupNorm convolution outputs, the per-(row, group) mean / rstd, the first block's output and the block output, the skip
+ * concatenations and the up / down sampled tensors.  Not bit-identical to cld_unet_forward_t (a direct form with its own summation
+ * order, no Winograd): within the forward parity bar of it. */
+int cld_unet_train_forward(cld_handle h, const float* params, const float* x, const float* cond, const int32_t* t_idx, float* eps,
+                           float* tape, size_t tape_bytes, int32_t B, void* workspace, size_t workspace_bytes, void* stream);
+
+/* The backward of cld_unet_train_forward for the cotangent d_eps [B,52,4] (the autograd step of dm_trainer.py:72-80 and
+ * guide_dm_trainer.py:127-183 through the U-Net).  Same params / x / tape as the forward (cond and t_idx are on the tape; they are
+ * accepted for symmetry).  Any of d_params (flat layout), dx [B,52,4], dcond [B,256] may be NULL.  d_params gets the gradient of all
+ * 148 tensors: accumulate = 0 overwrites them, 1 adds to them.  dx and dcond are always overwritten.  Weight gradients are split over
+ * row chunks and summed in a fixed order: the result is bit-identical run to run, and each row's dx / dcond does not depend on the
+ * other rows of the batch. */
+int cld_unet_backward(cld_handle h, const float* params, const float* x, const float* cond, const int32_t* t_idx, const float* tape,
+                      size_t tape_bytes, const float* d_eps, float* d_params, float* dx, float* dcond, int32_t accumulate, int32_t B,
+                      void* workspace, size_t workspace_bytes, void* stream);
+
 /* CLD_PRECISION_* the handle runs with. */
 int cld_get_precision(cld_handle h);
 
