@@ -144,6 +144,17 @@ SIGNATURES = {
     "cld_unet_train_workspace_bytes": (C.c_size_t, [_P, C.c_int32]),
     "cld_unet_train_forward": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_size_t, C.c_int32, _P, C.c_size_t, _P]),
     "cld_unet_backward": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_size_t, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, C.c_size_t, _P]),
+    "cld_vae_param_count": (C.c_int, [_P]),
+    "cld_vae_param_info": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
+                                     C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "cld_vae_param_floats": (C.c_size_t, [_P]),
+    "cld_vae_tape_bytes": (C.c_size_t, [_P, C.c_int32, C.c_int32]),
+    "cld_vae_train_workspace_bytes": (C.c_size_t, [_P, C.c_int32]),
+    "cld_vae_encode_train": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, C.c_int32, _P]),
+    "cld_vae_encode_backward": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_size_t, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, C.c_size_t,
+                                          _P]),
+    "cld_vae_decode_train": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_size_t, C.c_int32, _P]),
+    "cld_vae_decode_backward": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_size_t, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, C.c_size_t, _P]),
     "cld_get_precision": (C.c_int, [_P]),
     "cld_version": (C.c_char_p, []),
 }

@@ -2031,4 +2031,85 @@ int cld_unet_backward(cld_handle h, const float* params, const float* x, const f
     return CLD_OK;
 }
 
+/* ---- LSTM-VAE training (vae_train_kernels.hip) ---- */
+int cld_vae_param_count(cld_handle) { return kVaeParams; }
+
+int cld_vae_param_info(cld_handle h, int32_t i, const char** name, size_t* offset, size_t* numel, int32_t* shape, int32_t* ndim) {
+    if (i < 0 || i >= kVaeParams) return fail(h, CLD_ERR_ARG, "cld_vae_param_info: index out of range");
+    const TrainParam& p = vae_params()[i];
+    if (name) *name = p.name;
+    if (offset) *offset = p.offset;
+    if (numel) *numel = p.numel;
+    if (ndim) *ndim = p.ndim;
+    if (shape)
+        for (int d = 0; d < 3; ++d) shape[d] = d < p.ndim ? p.shape[d] : 1;
+    return CLD_OK;
+}
+
+size_t cld_vae_param_floats(cld_handle) { return vae_param_floats(); }
+
+size_t cld_vae_tape_bytes(cld_handle, int32_t part, int32_t B) {
+    return (B < 1 || (part != CLD_VAE_ENCODER && part != CLD_VAE_DECODER)) ? 0 : vae_tape_floats(B) * sizeof(float);
+}
+
+size_t cld_vae_train_workspace_bytes(cld_handle, int32_t B) { return B < 1 ? 0 : vae_ws_floats(B) * sizeof(float); }
+
+// ws == nullptr: the forward (no workspace)
+static int check_vae(cld_handle h, const char* fn, int part, int B, const float* params, const void* tape, size_t tape_bytes, const void* ws,
+                     size_t ws_bytes, bool backward) {
+    if (!h) return CLD_ERR_ARG;
+    if (h->precision != CLD_PRECISION_F32)
+        return fail(h, CLD_ERR_STATE, std::string(fn) + ": training runs in exact fp32 only (this handle is CLD_PRECISION_F16X2)");
+    if (B < 1 || B > (1 << 20)) return fail(h, CLD_ERR_ARG, std::string(fn) + ": B out of range [1, 2^20]");
+    if (!params) return fail(h, CLD_ERR_ARG, std::string(fn) + ": null pointer");
+    if (!tape || tape_bytes < cld_vae_tape_bytes(h, part, B)) return fail(h, CLD_ERR_WORKSPACE, std::string(fn) + ": tape too small");
+    if (backward && (!ws || ws_bytes < cld_vae_train_workspace_bytes(h, B)))
+        return fail(h, CLD_ERR_WORKSPACE, std::string(fn) + ": workspace too small");
+    if (reinterpret_cast<uintptr_t>(params) % 16 || reinterpret_cast<uintptr_t>(tape) % 16 || reinterpret_cast<uintptr_t>(ws) % 16)
+        return fail(h, CLD_ERR_ARG, std::string(fn) + ": params, workspace and tape must be 16-byte aligned");
+    return CLD_OK;
+}
+
+int cld_vae_encode_train(cld_handle h, const float* params, const float* x6, const float* cond, const float* drop_mask, float* mu,
+                         float* logvar, float* tape, size_t tape_bytes, int32_t B, void* stream) {
+    int rc = check_vae(h, "cld_vae_encode_train", CLD_VAE_ENCODER, B, params, tape, tape_bytes, nullptr, 0, false);
+    if (rc) return rc;
+    if (!x6 || !cond || !mu || !logvar) return fail(h, CLD_ERR_ARG, "cld_vae_encode_train: null pointer");
+    HIPCK(h, vae_train_forward(0, params, x6, cond, drop_mask, mu, logvar, tape, B, static_cast<hipStream_t>(stream)));
+    return CLD_OK;
+}
+
+int cld_vae_encode_backward(cld_handle h, const float* params, const float* x6, const float* cond, const float* drop_mask,
+                            const float* tape, size_t tape_bytes, const float* d_mu, const float* d_logvar, float* d_params, float* dx6,
+                            float* dcond, int32_t accumulate, int32_t B, void* workspace, size_t workspace_bytes, void* stream) {
+    int rc = check_vae(h, "cld_vae_encode_backward", CLD_VAE_ENCODER, B, params, tape, tape_bytes, workspace, workspace_bytes, true);
+    if (rc) return rc;
+    if (!x6 || !cond) return fail(h, CLD_ERR_ARG, "cld_vae_encode_backward: null pointer");
+    if (accumulate != 0 && accumulate != 1) return fail(h, CLD_ERR_ARG, "cld_vae_encode_backward: accumulate must be 0 or 1");
+    HIPCK(h, vae_train_backward(0, params, x6, cond, drop_mask, tape, d_mu, d_logvar, d_params, dx6, dcond, accumulate, B,
+                                static_cast<float*>(workspace), static_cast<hipStream_t>(stream)));
+    return CLD_OK;
+}
+
+int cld_vae_decode_train(cld_handle h, const float* params, const float* z, const float* cond, const float* drop_mask, float* act,
+                         float* tape, size_t tape_bytes, int32_t B, void* stream) {
+    int rc = check_vae(h, "cld_vae_decode_train", CLD_VAE_DECODER, B, params, tape, tape_bytes, nullptr, 0, false);
+    if (rc) return rc;
+    if (!z || !cond || !act) return fail(h, CLD_ERR_ARG, "cld_vae_decode_train: null pointer");
+    HIPCK(h, vae_train_forward(1, params, z, cond, drop_mask, act, nullptr, tape, B, static_cast<hipStream_t>(stream)));
+    return CLD_OK;
+}
+
+int cld_vae_decode_backward(cld_handle h, const float* params, const float* z, const float* cond, const float* drop_mask,
+                            const float* tape, size_t tape_bytes, const float* d_act, float* d_params, float* dz, float* dcond,
+                            int32_t accumulate, int32_t B, void* workspace, size_t workspace_bytes, void* stream) {
+    int rc = check_vae(h, "cld_vae_decode_backward", CLD_VAE_DECODER, B, params, tape, tape_bytes, workspace, workspace_bytes, true);
+    if (rc) return rc;
+    if (!z || !cond) return fail(h, CLD_ERR_ARG, "cld_vae_decode_backward: null pointer");
+    if (accumulate != 0 && accumulate != 1) return fail(h, CLD_ERR_ARG, "cld_vae_decode_backward: accumulate must be 0 or 1");
+    HIPCK(h, vae_train_backward(1, params, z, cond, drop_mask, tape, d_act, nullptr, d_params, dz, dcond, accumulate, B,
+                                static_cast<float*>(workspace), static_cast<hipStream_t>(stream)));
+    return CLD_OK;
+}
+
 }  // extern "C"

@@ -27,4 +27,28 @@ hipError_t train_forward(const float* params, const float* x, const float* cond,
 hipError_t train_backward(const float* params, const float* x, const float* tape, const float* d_eps, float* d_params, float* dx,
                           float* dcond, int accumulate, int B, float* ws, hipStream_t s);
 
+// The weight-gradient GEMM of the U-Net path (wgrad_kernel + wreduce_kernel: K split over at most 256 row chunks, summed in a
+// fixed order) for a Linear-shaped weight:
+//   dw[m om + c] (+)= sum_{b < rows, l < lp} P[(b lp + l) p_ld + m] G[(b lg + l - pd) g_ld + c]   (c < gc; G rows outside [0, lg) read 0)
+//   db[m], db2[m] (+)= sum_{b, l} P[(b lp + l) p_ld + m]                                           (each nullable)
+// `part` holds train_wgrad_part_floats(M, gc) floats.
+size_t train_wgrad_part_floats(int M, int gc);
+hipError_t train_wgrad(const float* P, int lp, int p_ld, int M, const float* G, int lg, int g_ld, int gc, int pd, int rows, float* dw,
+                       long om, float* db, float* db2, int accumulate, float* part, hipStream_t s);
+
+// ---- LSTM-VAE training (vae_train_kernels.hip) ----
+constexpr int kVaeParams = 26;
+const TrainParam* vae_params();       // kVaeParams entries in LSTMVAE state_dict order
+size_t vae_param_floats();
+size_t vae_tape_floats(int B);        // the encoder's and the decoder's tape have the same size
+size_t vae_ws_floats(int B);
+// part 0 (encoder): x = x6 [B,52,6] -> out = mu, out2 = logvar [B,52,4]; part 1 (decoder): x = z [B,52,4] -> out = act [B,52,2].
+// mask: [B,52,64] multiplied into layer 0's output where layer 1 reads it, or null.
+hipError_t vae_train_forward(int part, const float* params, const float* x, const float* cond, const float* mask, float* out,
+                             float* out2, float* tape, int B, hipStream_t s);
+// d_out / d_out2: the cotangents of out / out2 (nullable: zero).  d_params, dx, dcond nullable.
+hipError_t vae_train_backward(int part, const float* params, const float* x, const float* cond, const float* mask, const float* tape,
+                              const float* d_out, const float* d_out2, float* d_params, float* dx, float* dcond, int accumulate, int B,
+                              float* ws, hipStream_t s);
+
 }  // namespace cld

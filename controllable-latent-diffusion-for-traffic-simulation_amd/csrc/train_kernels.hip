@@ -185,6 +185,7 @@ struct WReduce {
     float* dw; long om, oc, ot;     // weight gradient of (m, tap, c) at dw[m om + c oc + tap ot]
     float* db;                      // the ones column: db[m] (null: dropped)
     int accumulate;
+    float* db2;                     // a second copy of the ones column (LSTM b_ih / b_hh), or null
 };
 
 __global__ __launch_bounds__(256) void wreduce_kernel(WReduce a) {
@@ -198,6 +199,7 @@ __global__ __launch_bounds__(256) void wreduce_kernel(WReduce a) {
         const int tap = n / a.gc, c = n - tap * a.gc;
         d = a.dw + m * a.om + c * a.oc + tap * a.ot;
     } else {
+        if (a.db2) a.db2[m] = a.accumulate ? a.db2[m] + s : s;
         if (!a.db) return;
         d = a.db + m;
     }
@@ -746,6 +748,27 @@ hipError_t train_backward(const float* params, const float* x, const float* tape
     mish_bwd_kernel<<<nblk(B * 128), 256, 0, s>>>(tp(T.a1), w.dm1, w.da1, B * 128);
     TRY(hipGetLastError());
     return wgrad(g, w.da1, 1, 128, 128, tp(T.te0), 1, 32, 32, 1, 0, 1, "model.time_mlp.1.weight", 32, 1, 0, "model.time_mlp.1.bias");
+}
+
+// The LSTM-VAE's weight gradients have at most 4 x 2 output tiles and K = 52 B: with 32 chunks a workgroup walks 208 K tiles at 2,048
+// rows, one workgroup per CU, latency-bound (~650 us per launch).  Up to 256 chunks put 8 workgroups on a CU and 26 K tiles in each.
+constexpr int kWgradChunks = 256;
+
+size_t train_wgrad_part_floats(int M, int gc) { return (size_t)kWgradChunks * M * (gc + 1); }
+
+hipError_t train_wgrad(const float* P, int lp, int p_ld, int M, const float* G, int lg, int g_ld, int gc, int pd, int rows, float* dw,
+                       long om, float* db, float* db2, int accumulate, float* part, hipStream_t s) {
+    int nchunk = rows < kWgradChunks ? rows : kWgradChunks;
+    const int rows_per = (rows + nchunk - 1) / nchunk;
+    nchunk = (rows + rows_per - 1) / rows_per;
+    const int N = gc + 1;
+    Wgrad a{P, lp, p_ld, M, G, lg, g_ld, gc, 1, pd, 1, rows, rows_per, N, part};
+    dim3 grid((N + BN - 1) / BN, (M + BM - 1) / BM, nchunk);
+    wgrad_kernel<<<grid, 256, 0, s>>>(a);
+    TRY(hipGetLastError());
+    WReduce r{part, nchunk, M, N, gc, 1, dw, om, 1, 0, db, accumulate, db2};
+    wreduce_kernel<<<nblk((long)M * N), 256, 0, s>>>(r);
+    return hipGetLastError();
 }
 
 }  // namespace cld

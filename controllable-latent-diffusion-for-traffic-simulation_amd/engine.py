@@ -32,18 +32,27 @@ def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
-def unet_param_table(lib=None, h=None):
-    """cld_unet_param_info for all 148 U-Net tensors: ([(name, offset, numel, shape)], flat buffer length in floats).  The table is
-    fixed by the architecture; it needs no handle and no device."""
+def _param_table(lib, h, model):
     lib = lib or _lib.load()
+    count, info, floats = (getattr(lib, f"cld_{model}_param_{s}") for s in ("count", "info", "floats"))
     out = []
     name, off, numel = C.c_char_p(), C.c_size_t(), C.c_size_t()
     shape, ndim = (C.c_int32 * 3)(), C.c_int32()
-    for i in range(int(lib.cld_unet_param_count(h))):
-        _lib.check(h, lib.cld_unet_param_info(h, i, C.byref(name), C.byref(off), C.byref(numel), shape, C.byref(ndim)),
-                   "cld_unet_param_info")
+    for i in range(int(count(h))):
+        _lib.check(h, info(h, i, C.byref(name), C.byref(off), C.byref(numel), shape, C.byref(ndim)), f"cld_{model}_param_info")
         out.append((name.value.decode(), int(off.value), int(numel.value), tuple(int(shape[d]) for d in range(ndim.value))))
-    return out, int(lib.cld_unet_param_floats(h))
+    return out, int(floats(h))
+
+
+def unet_param_table(lib=None, h=None):
+    """cld_unet_param_info for all 148 U-Net tensors: ([(name, offset, numel, shape)], flat buffer length in floats).  The table is
+    fixed by the architecture; it needs no handle and no device."""
+    return _param_table(lib, h, "unet")
+
+
+def vae_param_table(lib=None, h=None):
+    """cld_vae_param_info for all 26 LSTMVAE tensors, as unet_param_table."""
+    return _param_table(lib, h, "vae")
 
 
 class Engine:
@@ -643,6 +652,74 @@ class Engine:
                                                    _ptr(d_eps), _ptr(d_params), _ptr(dx), _ptr(dcond), int(bool(accumulate)), B,
                                                    ws, wsn, self._stream()), "cld_unet_backward")
         return dx, dcond
+
+    # ------------------------------------------------------------------ VAE training (exact fp32; cld_vae_*_train / cld_vae_*_backward)
+    def vae_param_table(self):
+        """[(name, offset, numel, shape)] of the 26 LSTMVAE tensors in the flat parameter buffer, and the buffer's length in floats."""
+        return vae_param_table(self.lib, self._h)
+
+    def _vae_workspace(self, B: int):
+        need = int(self.lib.cld_vae_train_workspace_bytes(self._h, B))
+        if getattr(self, "_vws", None) is None or self._vws.numel() < need:
+            self._vws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return C.c_void_p(self._vws.data_ptr()), C.c_size_t(self._vws.numel())
+
+    def _vae_args(self, x, width, cond, mask):
+        x = self._f32(x)
+        B = x.shape[0]
+        return (B, self._f32(x, (B, T, width)), self._f32(cond, (B, COND)),
+                None if mask is None else self._f32(mask, (B, T, 64)))
+
+    def vae_encode_train(self, params, x6, cond, mask=None):
+        """(mu, logvar) [B,52,4] of the encoder with the weights of `params` (flat fp32 device buffer, `vae_param_table` layout) and
+        the dropout mask [B,52,64] of layer 0's output (None: eval mode), plus the tape `vae_encode_backward` needs."""
+        B, x, cond, mask = self._vae_args(x6, 6, cond, mask)
+        mu, lv = (torch.empty(B, T, D, dtype=torch.float32, device=self.device) for _ in range(2))
+        tape = torch.empty(int(self.lib.cld_vae_tape_bytes(self._h, 0, B)), dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cld_vae_encode_train(self._h, _ptr(params), _ptr(x), _ptr(cond), _ptr(mask), _ptr(mu), _ptr(lv),
+                                                      _ptr(tape), tape.numel(), B, self._stream()), "cld_vae_encode_train")
+        return mu, lv, tape
+
+    def vae_encode_backward(self, params, x6, cond, mask, tape, d_mu, d_logvar, d_params=None, want_dx=True, want_dcond=False,
+                            accumulate=False):
+        """Gradients of the encoder for the cotangents d_mu / d_logvar [B,52,4] (None: zero) from the tape of `vae_encode_train` on the
+        same params / x6 / cond / mask.  d_params: flat fp32 device buffer whose encoder tensors receive (accumulate=False) or add
+        (True) the gradients, or None.  Returns (dx6 [B,52,6] or None, dcond [B,256] or None)."""
+        B, x, cond, mask = self._vae_args(x6, 6, cond, mask)
+        d_mu = None if d_mu is None else self._f32(d_mu, (B, T, D))
+        d_logvar = None if d_logvar is None else self._f32(d_logvar, (B, T, D))
+        dx = torch.empty_like(x) if want_dx else None
+        dcond = torch.empty_like(cond) if want_dcond else None
+        ws, wsn = self._vae_workspace(B)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cld_vae_encode_backward(self._h, _ptr(params), _ptr(x), _ptr(cond), _ptr(mask), _ptr(tape), tape.numel(),
+                                                         _ptr(d_mu), _ptr(d_logvar), _ptr(d_params), _ptr(dx), _ptr(dcond),
+                                                         int(bool(accumulate)), B, ws, wsn, self._stream()), "cld_vae_encode_backward")
+        return dx, dcond
+
+    def vae_decode_train(self, params, z, cond, mask=None):
+        """act [B,52,2] of the decoder with the weights of `params` and the dropout mask (None: eval mode), plus its tape."""
+        B, z, cond, mask = self._vae_args(z, D, cond, mask)
+        act = torch.empty(B, T, 2, dtype=torch.float32, device=self.device)
+        tape = torch.empty(int(self.lib.cld_vae_tape_bytes(self._h, 1, B)), dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cld_vae_decode_train(self._h, _ptr(params), _ptr(z), _ptr(cond), _ptr(mask), _ptr(act), _ptr(tape),
+                                                      tape.numel(), B, self._stream()), "cld_vae_decode_train")
+        return act, tape
+
+    def vae_decode_backward(self, params, z, cond, mask, tape, d_act, d_params=None, want_dz=True, want_dcond=False, accumulate=False):
+        """Gradients of the decoder for d_act [B,52,2]; as vae_encode_backward.  Returns (dz [B,52,4] or None, dcond or None)."""
+        B, z, cond, mask = self._vae_args(z, D, cond, mask)
+        d_act = self._f32(d_act, (B, T, 2))
+        dz = torch.empty_like(z) if want_dz else None
+        dcond = torch.empty_like(cond) if want_dcond else None
+        ws, wsn = self._vae_workspace(B)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cld_vae_decode_backward(self._h, _ptr(params), _ptr(z), _ptr(cond), _ptr(mask), _ptr(tape), tape.numel(),
+                                                         _ptr(d_act), _ptr(d_params), _ptr(dz), _ptr(dcond), int(bool(accumulate)), B,
+                                                         ws, wsn, self._stream()), "cld_vae_decode_backward")
+        return dz, dcond
 
     def log_prob(self, x_t, x_tm1, cond, t_idx: int):
         x_t = self._f32(x_t)

@@ -1,11 +1,13 @@
-"""Training surface of the denoiser: the U-Net's forward and backward on the HIP training path (include/cld.h,
-cld_unet_train_forward / cld_unet_backward) behind torch autograd.
+"""Training surface of the denoiser and of the LSTM-VAE: the U-Net's forward and backward on the HIP training path (include/cld.h,
+cld_unet_train_forward / cld_unet_backward) and the VAE's encoder / decoder forward and backward (cld_vae_*_train / cld_vae_*_backward)
+behind torch autograd.
 
 The reference trains `self.dm.parameters()` with Adam in two loops (src/trainers/dm_trainer.py:72-80 on
 `DmModel.compute_losses`, and src/trainers/guide_dm_trainer.py:127-183 `ppo_update` on `DmModel.log_prob` at t = 0).
 `TrainableDm` keeps the U-Net weights in ONE flat fp32 device tensor, exposed as `nn.Parameter` views under the reference's
 state_dict names, so `torch.optim.Adam(dm.parameters())` updates them in place and the next forward reads the new values with no
 host round trip.  The small loss heads (q_sample, MSE, the Normal log-density) are torch elementwise code around the U-Net.
+`TrainableVae` does the same for LSTMVAE (src/trainers/vae_trainer.py: Adam over the VAE's parameters on compute_vae_loss).
 Exact fp32 only: a "f16x2" engine refuses these calls.
 """
 from __future__ import annotations
@@ -14,10 +16,12 @@ import math
 from typing import Mapping, Optional
 
 import torch
+import torch.nn.functional as F
 
 from ._lib import CldError
 from .dm_model import DmModel
 from .engine import Engine, unet_param_table
+from .vae_model import VaeModel
 
 
 class UnetFn(torch.autograd.Function):
@@ -173,3 +177,179 @@ class TrainableDm:
         eng = Engine(n_timesteps=n, device=self.device, precision=precision)
         eng.load_state_dict(self.state_dict()).finalize()
         return DmModel(n_timesteps=n, device=self.device, engine=eng)
+
+
+# ====================================================================== the LSTM-VAE
+class VaeEncodeFn(torch.autograd.Function):
+    """(mu, logvar) = encoder(x6, cond) with the weights of `flat` and the dropout mask (None: eval mode); `params` are the views of
+    the encoder's 14 tensors, which receive the gradients."""
+
+    @staticmethod
+    def forward(ctx, x, cond, mask, engine: Engine, flat, table, *params):
+        mu, lv, tape = engine.vae_encode_train(flat, x, cond, mask)
+        ctx.engine, ctx.table, ctx.flat, ctx.mask, ctx.tape = engine, table, flat, mask, tape
+        ctx.save_for_backward(x.detach(), cond.detach())
+        return mu, lv
+
+    @staticmethod
+    def backward(ctx, d_mu, d_lv):
+        x, cond = ctx.saved_tensors
+        want_dp = any(ctx.needs_input_grad[6:])
+        d_flat = torch.empty_like(ctx.flat) if want_dp else None     # accumulate=0 writes every tensor of the encoder
+        dx, dcond = ctx.engine.vae_encode_backward(ctx.flat, x, cond, ctx.mask, ctx.tape,
+                                                   None if d_mu is None else d_mu.contiguous(), None if d_lv is None else d_lv.contiguous(),
+                                                   d_params=d_flat, want_dx=ctx.needs_input_grad[0], want_dcond=ctx.needs_input_grad[1])
+        ctx.tape = None
+        grads = [d_flat[off:off + n].view(shape) for (_, off, n, shape) in ctx.table] if want_dp else [None] * len(ctx.table)
+        return (dx, dcond, None, None, None, None, *grads)
+
+
+class VaeDecodeFn(torch.autograd.Function):
+    """act = decoder(z, cond) with the weights of `flat` and the dropout mask; `params` are the views of the decoder's 12 tensors."""
+
+    @staticmethod
+    def forward(ctx, z, cond, mask, engine: Engine, flat, table, *params):
+        act, tape = engine.vae_decode_train(flat, z, cond, mask)
+        ctx.engine, ctx.table, ctx.flat, ctx.mask, ctx.tape = engine, table, flat, mask, tape
+        ctx.save_for_backward(z.detach(), cond.detach())
+        return act
+
+    @staticmethod
+    def backward(ctx, d_act):
+        z, cond = ctx.saved_tensors
+        want_dp = any(ctx.needs_input_grad[6:])
+        d_flat = torch.empty_like(ctx.flat) if want_dp else None
+        dz, dcond = ctx.engine.vae_decode_backward(ctx.flat, z, cond, ctx.mask, ctx.tape, d_act.contiguous(), d_params=d_flat,
+                                                   want_dz=ctx.needs_input_grad[0], want_dcond=ctx.needs_input_grad[1])
+        ctx.tape = None
+        grads = [d_flat[off:off + n].view(shape) for (_, off, n, shape) in ctx.table] if want_dp else [None] * len(ctx.table)
+        return (dz, dcond, None, None, None, None, *grads)
+
+
+_VAE_KEYS = ("lstm_enc.", "lstm_dec.", "mu.", "logvar.")
+
+
+def _strip_vae(k: str) -> str:
+    for p in ("vae.lstmvae.", "lstmvae."):
+        if k.startswith(p):
+            return k[len(p):]
+    return k
+
+
+class TrainableVae:
+    """A trainable LSTMVAE (models/vae/lstm_vae.py:54-99) over the HIP training path, with VaeModel.compute_vae_loss.
+
+    `weights`: the LSTMVAE state_dict ('lstmvae.' / 'vae.lstmvae.' prefixes stripped; other keys, e.g. 'context_encoder.*', ignored).
+    The 26 tensors live in ONE flat fp32 device tensor (`flat`, the cld_vae_param_info layout) and are exposed as `nn.Parameter` views
+    under the reference names.  Like an nn.Module it starts in train mode: nn.LSTM's inter-layer dropout (p = `dropout`) is drawn on the
+    device per call; `eval()` turns it off; every call also takes explicit masks [B,52,64] (0 or 1 / (1 - p)).  `traj2z`, `lstm_dec`
+    and `forward` are differentiable with respect to the parameters and to x / z / context where those require grad (the encoder's and
+    the decoder's dcond add).  `to_vae_model()` gives a finalized VaeModel with the current weights for the sampling path."""
+
+    def __init__(self, weights: Mapping, device="cuda:0", dropout: float = 0.2):
+        self.device = torch.device(device)
+        self.p = float(dropout)
+        self.training = True
+        self.engine = Engine(device=device)       # the training calls read every weight from the flat buffer: no weights, no finalize
+        table, nflat = self.engine.vae_param_table()
+        self._flat = torch.zeros(nflat, dtype=torch.float32, device=self.device)
+        self._params = {name: torch.nn.Parameter(self._flat[off:off + n].view(shape)) for name, off, n, shape in table}
+        enc = [e for e in table if not e[0].startswith("lstm_dec.")]
+        dec = [e for e in table if e[0].startswith("lstm_dec.")]
+        self._enc = (enc, [self._params[e[0]] for e in enc])
+        self._dec = (dec, [self._params[e[0]] for e in dec])
+        self.load_state_dict(weights)
+
+    # ------------------------------------------------------------------ parameters and mode
+    @property
+    def flat(self) -> torch.Tensor:
+        """The flat fp32 device buffer the parameters are views of (cld_vae_param_info layout)."""
+        return self._flat
+
+    def named_parameters(self):
+        return iter(self._params.items())
+
+    def parameters(self):
+        return iter(self._params.values())
+
+    def state_dict(self) -> dict:
+        return {k: p.detach().clone() for k, p in self._params.items()}
+
+    def load_state_dict(self, sd: Mapping, strict: bool = True):
+        sd = {_strip_vae(k): v for k, v in sd.items()}
+        missing = [k for k in self._params if k not in sd]
+        unknown = [k for k in sd if k not in self._params and k.startswith(_VAE_KEYS)]
+        if strict and (missing or unknown):
+            raise CldError(f"load_state_dict: missing {missing[:4]}, unknown {unknown[:4]}")
+        with torch.no_grad():
+            for k, p in self._params.items():
+                if k in sd:
+                    v = torch.as_tensor(sd[k]).to(device=self.device, dtype=torch.float32)
+                    if tuple(v.shape) != tuple(p.shape):
+                        raise CldError(f"load_state_dict: '{k}' expects shape {tuple(p.shape)}, got {tuple(v.shape)}")
+                    p.copy_(v)
+        return self
+
+    def zero_grad(self, set_to_none: bool = True):
+        for p in self._params.values():
+            if set_to_none:
+                p.grad = None
+            elif p.grad is not None:
+                p.grad.zero_()
+
+    def train(self, mode: bool = True):
+        self.training = bool(mode)
+        return self
+
+    def eval(self):
+        return self.train(False)
+
+    # ------------------------------------------------------------------ the model
+    def _mask(self, B: int, mask):
+        if mask is not None:
+            return torch.as_tensor(mask).to(self.device, torch.float32)
+        if not self.training or self.p == 0.0:
+            return None
+        return (torch.rand(B, 52, 64, device=self.device) >= self.p).float() / (1.0 - self.p)
+
+    def _f32(self, t):
+        return torch.as_tensor(t).to(self.device, torch.float32)
+
+    def traj2z(self, x, context, noise=None, masks=None):
+        """lstm_vae.py:87-99 -> (z, mu, logvar) [B,52,4]; `noise` replaces the reference's randn_like draw (drawn on the device when
+        omitted); `masks`: the encoder's dropout mask.  The reparametrisation is torch autograd."""
+        x, cond = self._f32(x), self._f32(context)
+        B = x.shape[0]
+        table, params = self._enc
+        mu, lv = VaeEncodeFn.apply(x, cond, self._mask(B, masks), self.engine, self._flat, table, *params)
+        noise = torch.randn(B, 52, 4, device=self.device) if noise is None else self._f32(noise)
+        return mu + noise * torch.exp(0.5 * lv), mu, lv
+
+    def lstm_dec(self, z, context, mask=None):
+        """lstm_vae.py:44-52 -> act [B,52,2]."""
+        z, cond = self._f32(z), self._f32(context)
+        table, params = self._dec
+        return VaeDecodeFn.apply(z, cond, self._mask(z.shape[0], mask), self.engine, self._flat, table, *params)
+
+    def forward(self, x, context, noise=None, masks=None):
+        """lstm_vae.py:82-85 -> (act [B,52,2], mu, logvar); masks = (encoder mask, decoder mask) or None."""
+        me, md = (None, None) if masks is None else masks
+        z, mu, lv = self.traj2z(x, context, noise, me)
+        return self.lstm_dec(z, context, md), mu, lv
+
+    __call__ = forward
+
+    @staticmethod
+    def compute_vae_loss(input, output, mu, logvar, beta):
+        """vae_model.py:89-99 -> (loss, recon, kld): recon = mse(input[..., 4:6], output), kld = -0.5 sum(1 + lv - mu^2 - e^lv) / (B T)."""
+        recon = F.mse_loss(input[..., 4:6], output)
+        B, T, _ = mu.shape
+        kld = -0.5 * torch.sum(1 + logvar - mu.pow(2) - logvar.exp()) / (B * T)
+        return recon + beta * kld, recon, kld
+
+    # ------------------------------------------------------------------ sampling with the current weights
+    def to_vae_model(self) -> VaeModel:
+        """A VaeModel (its own finalized Engine) holding the current weights, for traj2z / lstm_dec / decode on the sampling path.
+        Call it again after optimiser steps.  Its state_dict() also loads into a DmModel's shared engine."""
+        vae = VaeModel(device=self.device)
+        return vae.load_state_dict(self.state_dict())

@@ -68,7 +68,7 @@ class VaeModel:
         return aux_info, self.get_state_and_action_from_data_batch(batch, scaled=True), sa
 
     def forward(self, batch, beta=None, noise=None):
-        """VaeModel.forward (vae_model.py:64-82), forward values only (training is out of scope): pre_vae -> lstmvae ->
+        """VaeModel.forward (vae_model.py:64-82), forward values only (training: cld_amd.train.TrainableVae): pre_vae -> lstmvae ->
         convert_action_to_state_and_action -> descale, and the loss terms of compute_vae_loss; the reference's dict keys."""
         aux_info, sa_scaled, _ = self.pre_vae(batch)
         recon_act, mu, logvar = self.lstmvae(sa_scaled, aux_info["cond_feat"], noise)

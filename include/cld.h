@@ -556,6 +556,56 @@ int cld_unet_backward(cld_handle h, const float* params, const float* x, const f
                       size_t tape_bytes, const float* d_eps, float* d_params, float* dx, float* dcond, int32_t accumulate, int32_t B,
                       void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- LSTM-VAE training (exact fp32): the reference's `vae` stage (train.py:10-20; src/trainers/vae_trainer.py: Adam over
+ * self.vae.parameters() on VaeModel.compute_vae_loss, vae_model.py:65-99).  The encoder's and the decoder's forward from weights held in a
+ * DEVICE buffer, each keeping a tape, and their backward: data gradients and the weight gradients of all 26 LSTMVAE tensors.  The
+ * reparametrisation z = mu + noise exp(0.5 logvar), the loss and the optimiser stay the caller's.  The calls read no weights from the
+ * handle (one without any weights trains); a CLD_PRECISION_F16X2 handle refuses them with CLD_ERR_STATE.  The table and size queries
+ * need no handle (h may be NULL).
+ *
+ * Parameter table: the 26 tensors of LSTMVAE's state_dict (lstm_vae.py:54-80) in its order -- lstm_enc.lstm.{weight_ih, weight_hh,
+ * bias_ih, bias_hh}_l{0,1}, lstm_enc.cond2hidden.*, the same 8 under lstm_dec.lstm.*, lstm_dec.cond2hidden.*, lstm_dec.hid2act.*, mu.*,
+ * logvar.* (136,458 values) -- each at an offset (in floats, a multiple of 64) into one flat fp32 buffer, in the reference layouts
+ * (weight_ih [256, in] and weight_hh [256, 64] with gate rows i, f, g, o; Linear [out, in]).  `shape` gets 3 entries (1 past ndim).
+ *
+ * Dropout: in training mode nn.LSTM(num_layers = 2, dropout = 0.2) drops layer 0's output where it enters layer 1, scaled by 1 / (1 - p);
+ * the recurrence and the top layer's output are not dropped.  `drop_mask` [B,52,64] (DEVICE, or NULL = eval mode) holds that factor per
+ * element (0 or 1 / (1 - p)); it is multiplied into layer 0's h on that path only.  The backward takes the same mask. */
+#define CLD_VAE_ENCODER 0
+#define CLD_VAE_DECODER 1
+int cld_vae_param_count(cld_handle h);                   /* 26 */
+int cld_vae_param_info(cld_handle h, int32_t i, const char** name, size_t* offset, size_t* numel, int32_t* shape, int32_t* ndim);
+size_t cld_vae_param_floats(cld_handle h);               /* length of the flat buffer (> 136,458 values: alignment) */
+/* Tape bytes of the encoder's (part CLD_VAE_ENCODER) or the decoder's (CLD_VAE_DECODER) forward for B rows: per step and layer the
+ * activated gates and c, h of both layers from h0 on, and layer 1's masked input (173,568 bytes per row for either part; 0 for another
+ * part or B < 1).  Workspace bytes of either backward. */
+size_t cld_vae_tape_bytes(cld_handle h, int32_t part, int32_t B);
+size_t cld_vae_train_workspace_bytes(cld_handle h, int32_t B);
+
+/* (mu, logvar) [B,52,4] = the encoder and its heads (lstm_vae.py:6-26, 87-93) on x6 [B,52,6] (scaled state and action) and cond [B,256],
+ * with the weights of `params` (DEVICE, the flat layout above).  Writes the tape (DEVICE, caller-owned, 16-byte aligned, >=
+ * cld_vae_tape_bytes(h, CLD_VAE_ENCODER, B)).  Without a mask it agrees with cld_traj2z within the encoder's parity bar (not bit for bit:
+ * libm sigmoid / tanh, a separate head sum). */
+int cld_vae_encode_train(cld_handle h, const float* params, const float* x6, const float* cond, const float* drop_mask, float* mu,
+                         float* logvar, float* tape, size_t tape_bytes, int32_t B, void* stream);
+/* The backward of cld_vae_encode_train for the cotangents d_mu, d_logvar [B,52,4] (either may be NULL: zero), from its tape with the same
+ * params / x6 / cond / drop_mask.  d_params (flat layout) gets the gradients of the encoder's 14 tensors (lstm_enc.*, mu.*, logvar.*; the
+ * others are not touched): accumulate = 0 overwrites them, 1 adds to them.  b_ih and b_hh get the same gradient, sum dgates.  dx6
+ * [B,52,6] and dcond [B,256] are overwritten.  Any of d_params, dx6, dcond may be NULL.  Weight gradients are summed over row chunks in a
+ * fixed order (no float atomics): bit-identical run to run; a row's dx6 / dcond does not depend on the other rows. */
+int cld_vae_encode_backward(cld_handle h, const float* params, const float* x6, const float* cond, const float* drop_mask,
+                            const float* tape, size_t tape_bytes, const float* d_mu, const float* d_logvar, float* d_params, float* dx6,
+                            float* dcond, int32_t accumulate, int32_t B, void* workspace, size_t workspace_bytes, void* stream);
+/* act [B,52,2] = the decoder (lstm_vae.py:28-52) on z [B,52,4] and cond [B,256]; tape >= cld_vae_tape_bytes(h, CLD_VAE_DECODER, B).
+ * Without a mask it agrees with cld_lstm_decode within the decoder's parity bar. */
+int cld_vae_decode_train(cld_handle h, const float* params, const float* z, const float* cond, const float* drop_mask, float* act,
+                         float* tape, size_t tape_bytes, int32_t B, void* stream);
+/* The backward of cld_vae_decode_train for d_act [B,52,2]: the gradients of the decoder's 12 tensors (lstm_dec.*) into d_params, dz
+ * [B,52,4], dcond [B,256]; the rules of cld_vae_encode_backward. */
+int cld_vae_decode_backward(cld_handle h, const float* params, const float* z, const float* cond, const float* drop_mask,
+                            const float* tape, size_t tape_bytes, const float* d_act, float* d_params, float* dz, float* dcond,
+                            int32_t accumulate, int32_t B, void* workspace, size_t workspace_bytes, void* stream);
+
 /* CLD_PRECISION_* the handle runs with. */
 int cld_get_precision(cld_handle h);
 
