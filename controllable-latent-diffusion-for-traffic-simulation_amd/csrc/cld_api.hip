@@ -21,17 +21,6 @@ namespace {
 constexpr int T = 52, D = 4, COND = 256, TE = 32, NCB = 1792, ACT = 3328;   // ACT floats/agent/buffer
 constexpr int NBUF = 8;
 
-struct BlockDef { const char* name; int cin, cout, L; };
-// the 12 residual blocks in execution order (temporal.py:84-115,148-167)
-const BlockDef kBlocks[12] = {
-    {"model.downs.0.0", 4, 64, 52},   {"model.downs.0.1", 64, 64, 52},
-    {"model.downs.1.0", 64, 128, 26}, {"model.downs.1.1", 128, 128, 26},
-    {"model.downs.2.0", 128, 256, 13}, {"model.downs.2.1", 256, 256, 13},
-    {"model.mid_block1", 256, 256, 13}, {"model.mid_block2", 256, 256, 13},
-    {"model.ups.0.0", 512, 128, 13},  {"model.ups.0.1", 128, 128, 13},
-    {"model.ups.1.0", 256, 64, 26},   {"model.ups.1.1", 64, 64, 26},
-};
-
 struct ConvLayer {
     ConvGeom g{};        // kc / nwn / ks are filled per launch by pick_tiling()
     bool has_a = false, has_b = false;   // which tilings have a kernel instance
@@ -126,41 +115,10 @@ float* upload(cld_handle h, const std::vector<float>& v, hipStream_t s, hipError
 void add_expect(cld_handle h) {
     auto& e = h->expect;
     auto lin = [&](const std::string& p, int o, int i) { e[p + ".weight"] = (size_t)o * i; e[p + ".bias"] = o; };
-    auto conv = [&](const std::string& p, int o, int i, int k) { e[p + ".weight"] = (size_t)o * i * k; e[p + ".bias"] = o; };
     auto gn = [&](const std::string& p, int c) { e[p + ".weight"] = c; e[p + ".bias"] = c; };
-    lin("model.time_mlp.1", 128, 32);
-    lin("model.time_mlp.3", 32, 128);
-    for (const auto& b : kBlocks) {
-        const std::string p = b.name;
-        lin(p + ".time_mlp.1", b.cout, COND + TE);
-        conv(p + ".blocks.0.block.0", b.cout, b.cin, 5);
-        gn(p + ".blocks.0.block.2", b.cout);
-        conv(p + ".blocks.1.block.0", b.cout, b.cout, 5);
-        gn(p + ".blocks.1.block.2", b.cout);
-        if (b.cin != b.cout) conv(p + ".residual_conv", b.cout, b.cin, 1);
-    }
-    conv("model.downs.0.2.conv", 64, 64, 3);
-    conv("model.downs.1.2.conv", 128, 128, 3);
-    conv("model.ups.0.2.conv", 128, 128, 4);
-    conv("model.ups.1.2.conv", 64, 64, 4);
-    conv("model.final_conv.0.block.0", 64, 64, 5);
-    gn("model.final_conv.0.block.2", 64);
-    conv("model.final_conv.1", 4, 64, 1);
-    // decoder (lstm_vae.py:28-43)
-    e["lstm_dec.lstm.weight_ih_l0"] = 256 * 4;  e["lstm_dec.lstm.weight_hh_l0"] = 256 * 64;
-    e["lstm_dec.lstm.bias_ih_l0"] = 256;        e["lstm_dec.lstm.bias_hh_l0"] = 256;
-    e["lstm_dec.lstm.weight_ih_l1"] = 256 * 64; e["lstm_dec.lstm.weight_hh_l1"] = 256 * 64;
-    e["lstm_dec.lstm.bias_ih_l1"] = 256;        e["lstm_dec.lstm.bias_hh_l1"] = 256;
-    e["lstm_dec.cond2hidden.weight"] = 64 * 256; e["lstm_dec.cond2hidden.bias"] = 64;
-    e["lstm_dec.hid2act.weight"] = 2 * 64;       e["lstm_dec.hid2act.bias"] = 2;
-    // encoder + latent heads (lstm_vae.py:6-19,82-83)
-    e["lstm_enc.lstm.weight_ih_l0"] = 256 * 6;  e["lstm_enc.lstm.weight_hh_l0"] = 256 * 64;
-    e["lstm_enc.lstm.bias_ih_l0"] = 256;        e["lstm_enc.lstm.bias_hh_l0"] = 256;
-    e["lstm_enc.lstm.weight_ih_l1"] = 256 * 64; e["lstm_enc.lstm.weight_hh_l1"] = 256 * 64;
-    e["lstm_enc.lstm.bias_ih_l1"] = 256;        e["lstm_enc.lstm.bias_hh_l1"] = 256;
-    e["lstm_enc.cond2hidden.weight"] = 64 * 256; e["lstm_enc.cond2hidden.bias"] = 64;
-    e["mu.weight"] = 4 * 64;     e["mu.bias"] = 4;
-    e["logvar.weight"] = 4 * 64; e["logvar.bias"] = 4;
+    // the U-Net and the LSTM-VAE: the tables of the training paths (train.h) are the reference's state_dicts
+    for (int i = 0; i < kTrainParams; ++i) e[train_params()[i].name] = train_params()[i].numel;
+    for (int i = 0; i < kVaeParams; ++i) e[vae_params()[i].name] = vae_params()[i].numel;
     // ContextEncoder (models/context_utils.py:8-38): two base_models.MLP (`_model` Sequential: Linear, LayerNorm, ReLU, ...)
     // and torchvision resnet18 under map_encoder.encoder_heads.map_model (base_models.py:559-614)
     auto mlp = [&](const std::string& p, int d_in, std::initializer_list<int> hidden, int d_out) {
@@ -1975,12 +1933,11 @@ int cld_world_step(cld_handle h, const float* traj, const float* centroid, const
     return CLD_OK;
 }
 
-/* ---- U-Net training (train_kernels.hip) ---- */
-int cld_unet_param_count(cld_handle) { return kTrainParams; }
-
-int cld_unet_param_info(cld_handle h, int32_t i, const char** name, size_t* offset, size_t* numel, int32_t* shape, int32_t* ndim) {
-    if (i < 0 || i >= kTrainParams) return fail(h, CLD_ERR_ARG, "cld_unet_param_info: index out of range");
-    const TrainParam& p = train_params()[i];
+/* ---- training: what the U-Net and the LSTM-VAE entry points share ---- */
+static int param_info(cld_handle h, const char* fn, const TrainParam* table, int count, int32_t i, const char** name, size_t* offset,
+                      size_t* numel, int32_t* shape, int32_t* ndim) {
+    if (i < 0 || i >= count) return fail(h, CLD_ERR_ARG, std::string(fn) + ": index out of range");
+    const TrainParam& p = table[i];
     if (name) *name = p.name;
     if (offset) *offset = p.offset;
     if (numel) *numel = p.numel;
@@ -1990,6 +1947,30 @@ int cld_unet_param_info(cld_handle h, int32_t i, const char** name, size_t* offs
     return CLD_OK;
 }
 
+// the checks every training call starts with: a handle, exact fp32
+static int check_f32(cld_handle h, const char* fn) {
+    if (!h) return CLD_ERR_ARG;
+    if (h->precision != CLD_PRECISION_F32)
+        return fail(h, CLD_ERR_STATE, std::string(fn) + ": training runs in exact fp32 only (this handle is CLD_PRECISION_F16X2)");
+    return CLD_OK;
+}
+static int check_rows(cld_handle h, const char* fn, int B) {
+    if (B < 1 || B > (1 << 20)) return fail(h, CLD_ERR_ARG, std::string(fn) + ": B out of range [1, 2^20]");
+    return CLD_OK;
+}
+static bool misaligned(std::initializer_list<const void*> ptrs) {
+    for (const void* p : ptrs)
+        if (reinterpret_cast<uintptr_t>(p) % 16) return true;
+    return false;
+}
+
+/* ---- U-Net training (train_kernels.hip) ---- */
+int cld_unet_param_count(cld_handle) { return kTrainParams; }
+
+int cld_unet_param_info(cld_handle h, int32_t i, const char** name, size_t* offset, size_t* numel, int32_t* shape, int32_t* ndim) {
+    return param_info(h, "cld_unet_param_info", train_params(), kTrainParams, i, name, offset, numel, shape, ndim);
+}
+
 size_t cld_unet_param_floats(cld_handle) { return train_param_floats(); }
 
 size_t cld_unet_tape_bytes(cld_handle, int32_t B) { return B < 1 ? 0 : train_tape_floats(B) * sizeof(float); }
@@ -1997,14 +1978,12 @@ size_t cld_unet_tape_bytes(cld_handle, int32_t B) { return B < 1 ? 0 : train_tap
 size_t cld_unet_train_workspace_bytes(cld_handle, int32_t B) { return B < 1 ? 0 : train_ws_floats(B) * sizeof(float); }
 
 static int check_train(cld_handle h, const char* fn, int B, const void* tape, size_t tape_bytes, const void* ws, size_t ws_bytes) {
-    if (!h) return CLD_ERR_ARG;
-    if (h->precision != CLD_PRECISION_F32)
-        return fail(h, CLD_ERR_STATE, std::string(fn) + ": training runs in exact fp32 only (this handle is CLD_PRECISION_F16X2)");
+    if (int rc = check_f32(h, fn)) return rc;
     if (!h->finalized || !h->has_unet) return fail(h, CLD_ERR_STATE, std::string(fn) + ": the handle has no finalized U-Net weights (model.*)");
-    if (B < 1 || B > (1 << 20)) return fail(h, CLD_ERR_ARG, std::string(fn) + ": B out of range [1, 2^20]");
+    if (int rc = check_rows(h, fn, B)) return rc;
     if (!tape || tape_bytes < cld_unet_tape_bytes(h, B)) return fail(h, CLD_ERR_WORKSPACE, std::string(fn) + ": tape too small");
     if (!ws || ws_bytes < cld_unet_train_workspace_bytes(h, B)) return fail(h, CLD_ERR_WORKSPACE, std::string(fn) + ": workspace too small");
-    if (reinterpret_cast<uintptr_t>(ws) % 16 || reinterpret_cast<uintptr_t>(tape) % 16)
+    if (misaligned({ws, tape}))
         return fail(h, CLD_ERR_ARG, std::string(fn) + ": workspace and tape must be 16-byte aligned");
     return CLD_OK;
 }
@@ -2035,15 +2014,7 @@ int cld_unet_backward(cld_handle h, const float* params, const float* x, const f
 int cld_vae_param_count(cld_handle) { return kVaeParams; }
 
 int cld_vae_param_info(cld_handle h, int32_t i, const char** name, size_t* offset, size_t* numel, int32_t* shape, int32_t* ndim) {
-    if (i < 0 || i >= kVaeParams) return fail(h, CLD_ERR_ARG, "cld_vae_param_info: index out of range");
-    const TrainParam& p = vae_params()[i];
-    if (name) *name = p.name;
-    if (offset) *offset = p.offset;
-    if (numel) *numel = p.numel;
-    if (ndim) *ndim = p.ndim;
-    if (shape)
-        for (int d = 0; d < 3; ++d) shape[d] = d < p.ndim ? p.shape[d] : 1;
-    return CLD_OK;
+    return param_info(h, "cld_vae_param_info", vae_params(), kVaeParams, i, name, offset, numel, shape, ndim);
 }
 
 size_t cld_vae_param_floats(cld_handle) { return vae_param_floats(); }
@@ -2057,15 +2028,13 @@ size_t cld_vae_train_workspace_bytes(cld_handle, int32_t B) { return B < 1 ? 0 :
 // ws == nullptr: the forward (no workspace)
 static int check_vae(cld_handle h, const char* fn, int part, int B, const float* params, const void* tape, size_t tape_bytes, const void* ws,
                      size_t ws_bytes, bool backward) {
-    if (!h) return CLD_ERR_ARG;
-    if (h->precision != CLD_PRECISION_F32)
-        return fail(h, CLD_ERR_STATE, std::string(fn) + ": training runs in exact fp32 only (this handle is CLD_PRECISION_F16X2)");
-    if (B < 1 || B > (1 << 20)) return fail(h, CLD_ERR_ARG, std::string(fn) + ": B out of range [1, 2^20]");
+    if (int rc = check_f32(h, fn)) return rc;
+    if (int rc = check_rows(h, fn, B)) return rc;
     if (!params) return fail(h, CLD_ERR_ARG, std::string(fn) + ": null pointer");
     if (!tape || tape_bytes < cld_vae_tape_bytes(h, part, B)) return fail(h, CLD_ERR_WORKSPACE, std::string(fn) + ": tape too small");
     if (backward && (!ws || ws_bytes < cld_vae_train_workspace_bytes(h, B)))
         return fail(h, CLD_ERR_WORKSPACE, std::string(fn) + ": workspace too small");
-    if (reinterpret_cast<uintptr_t>(params) % 16 || reinterpret_cast<uintptr_t>(tape) % 16 || reinterpret_cast<uintptr_t>(ws) % 16)
+    if (misaligned({params, tape, ws}))
         return fail(h, CLD_ERR_ARG, std::string(fn) + ": params, workspace and tape must be 16-byte aligned");
     return CLD_OK;
 }

@@ -12,9 +12,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <map>
 #include <string>
-#include <vector>
 
 #include "train.h"
 
@@ -46,6 +44,34 @@ __device__ __forceinline__ float mish_grad(float u) {
     return n * q + u * (e / (1.0f + e)) * (4.0f * (n + 1.0f) * q * q);
 }
 
+// The 64 x 64 tile core of the two GEMM kernels: 4 waves as 2 x 2, each with 2 x 2 MFMA tiles of 16 x 16 and NACC accumulator sets.
+typedef v4f TileAcc[NACC][2][2];
+
+__device__ __forceinline__ void tile_zero(TileAcc& acc) {
+    for (int q = 0; q < NACC; ++q)
+        for (int i = 0; i < 2; ++i)
+            for (int j = 0; j < 2; ++j) acc[q][i][j] = v4f{0.f, 0.f, 0.f, 0.f};
+}
+
+// acc += As^T Bs over one staged K tile (As[k][m], Bs[k][n]); k-step ks / 4 goes to accumulator set ks / 4
+__device__ __forceinline__ void tile_mfma(TileAcc& acc, const float (&As)[BK][LDS_LD], const float (&Bs)[BK][LDS_LD], int lane, int wm, int wn) {
+#pragma unroll
+    for (int ks = 0; ks < BK; ks += 4) {
+        const int kr = ks + (lane >> 4);
+        float av[2], bv[2];
+        for (int i = 0; i < 2; ++i) av[i] = As[kr][wm * 32 + i * 16 + (lane & 15)];
+        for (int j = 0; j < 2; ++j) bv[j] = Bs[kr][wn * 32 + j * 16 + (lane & 15)];
+        for (int i = 0; i < 2; ++i)
+            for (int j = 0; j < 2; ++j) acc[ks / 4][i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i], bv[j], acc[ks / 4][i][j], 0, 0, 0);
+    }
+}
+
+// the pairwise sum of the four sets, left in acc[0]
+__device__ __forceinline__ void tile_sum(TileAcc& acc) {
+    for (int i = 0; i < 2; ++i)
+        for (int j = 0; j < 2; ++j) acc[0][i][j] = (acc[0][i][j] + acc[1][i][j]) + (acc[2][i][j] + acc[3][i][j]);
+}
+
 struct ConvGemm {
     const float* in; int lin, cin, in_ld, mode, s, p, ntap;
     const float* wp; const float* bias;
@@ -60,10 +86,8 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(ConvGemm a) {
     const int K = a.ntap * a.cin;
     const long m0 = (long)blockIdx.y * BM;
     const int n0 = blockIdx.x * BN;
-    v4f acc[NACC][2][2];
-    for (int q = 0; q < NACC; ++q)
-        for (int i = 0; i < 2; ++i)
-            for (int j = 0; j < 2; ++j) acc[q][i][j] = v4f{0.f, 0.f, 0.f, 0.f};
+    TileAcc acc;
+    tile_zero(acc);
     for (int k0 = 0; k0 < K; k0 += BK) {
         for (int i = 0; i < 4; ++i) {
             const int e = tid + i * 256, r = e >> 4, kq = e & 15;
@@ -92,19 +116,10 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(ConvGemm a) {
             Bs[kq][n] = (kk < K && nn < a.N) ? a.wp[(long)kk * a.N + nn] : 0.f;
         }
         __syncthreads();
-#pragma unroll
-        for (int ks = 0; ks < BK; ks += 4) {
-            const int kr = ks + (lane >> 4);
-            float av[2], bv[2];
-            for (int i = 0; i < 2; ++i) av[i] = As[kr][wm * 32 + i * 16 + (lane & 15)];
-            for (int j = 0; j < 2; ++j) bv[j] = Bs[kr][wn * 32 + j * 16 + (lane & 15)];
-            for (int i = 0; i < 2; ++i)
-                for (int j = 0; j < 2; ++j) acc[ks / 4][i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i], bv[j], acc[ks / 4][i][j], 0, 0, 0);
-        }
+        tile_mfma(acc, As, Bs, lane, wm, wn);
         __syncthreads();
     }
-    for (int i = 0; i < 2; ++i)
-        for (int j = 0; j < 2; ++j) acc[0][i][j] = (acc[0][i][j] + acc[1][i][j]) + (acc[2][i][j] + acc[3][i][j]);
+    tile_sum(acc);
     for (int i = 0; i < 2; ++i)
         for (int j = 0; j < 2; ++j)
             for (int r = 0; r < 4; ++r) {
@@ -133,10 +148,8 @@ __global__ __launch_bounds__(256) void wgrad_kernel(Wgrad a) {
     const int z = blockIdx.z, b0 = z * a.rows_per, b1 = min(a.rows, b0 + a.rows_per);
     const long kbase = (long)b0 * a.lp, K = (long)(b1 - b0) * a.lp;
     const int m0 = blockIdx.y * BM, n0 = blockIdx.x * BN, NG = a.ntap * a.gc;
-    v4f acc[NACC][2][2];
-    for (int q = 0; q < NACC; ++q)
-        for (int i = 0; i < 2; ++i)
-            for (int j = 0; j < 2; ++j) acc[q][i][j] = v4f{0.f, 0.f, 0.f, 0.f};
+    TileAcc acc;
+    tile_zero(acc);
     for (long k0 = 0; k0 < K; k0 += BK) {
         for (int i = 0; i < 4; ++i) {
             const int e = tid + i * 256, kq = e >> 6, r = e & 63, mm = m0 + r;
@@ -159,19 +172,10 @@ __global__ __launch_bounds__(256) void wgrad_kernel(Wgrad a) {
             Bs[kq][n] = v;
         }
         __syncthreads();
-#pragma unroll
-        for (int ks = 0; ks < BK; ks += 4) {
-            const int kr = ks + (lane >> 4);
-            float av[2], bv[2];
-            for (int i = 0; i < 2; ++i) av[i] = As[kr][wm * 32 + i * 16 + (lane & 15)];
-            for (int j = 0; j < 2; ++j) bv[j] = Bs[kr][wn * 32 + j * 16 + (lane & 15)];
-            for (int i = 0; i < 2; ++i)
-                for (int j = 0; j < 2; ++j) acc[ks / 4][i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i], bv[j], acc[ks / 4][i][j], 0, 0, 0);
-        }
+        tile_mfma(acc, As, Bs, lane, wm, wn);
         __syncthreads();
     }
-    for (int i = 0; i < 2; ++i)
-        for (int j = 0; j < 2; ++j) acc[0][i][j] = (acc[0][i][j] + acc[1][i][j]) + (acc[2][i][j] + acc[3][i][j]);
+    tile_sum(acc);
     for (int i = 0; i < 2; ++i)
         for (int j = 0; j < 2; ++j)
             for (int r = 0; r < 4; ++r) {
@@ -361,75 +365,40 @@ __global__ __launch_bounds__(256) void copy2d_kernel(const float* src, int sld, 
     *d = accumulate ? *d + v : v;
 }
 
-inline unsigned nblk(long n) { return (unsigned)((n + 255) / 256); }
-
 // ------------------------------------------------------------------ parameter table
-struct Table {
-    std::vector<TrainParam> p;
-    std::vector<std::string> names;
-    std::map<std::string, int> idx;
-    size_t floats = 0;
-    Table() {
-        auto add = [&](const std::string& n, std::vector<int> shape) {
-            TrainParam t{};
-            size_t numel = 1;
-            for (size_t i = 0; i < shape.size(); ++i) { t.shape[i] = shape[i]; numel *= shape[i]; }
-            t.ndim = (int)shape.size();
-            t.numel = numel;
-            t.offset = floats;
-            floats += (numel + kTrainAlign - 1) / kTrainAlign * kTrainAlign;
-            idx[n] = (int)p.size();
-            names.push_back(n);
-            p.push_back(t);
-        };
-        auto res = [&](const std::string& pre, int cin, int c) {     // temporal.py:16-45 ResidualTemporalMapBlockConcat
+struct UnetTable : ParamTable {
+    UnetTable() {
+        add("model.time_mlp.1.weight", {128, 32}); add("model.time_mlp.1.bias", {128});
+        add("model.time_mlp.3.weight", {32, 128}); add("model.time_mlp.3.bias", {32});
+        // the blocks' execution order is the state_dict's; the re-sampling conv of a level follows its second block
+        // (temporal.py:84-115: Downsample1d Conv1d k3 after downs.0 / downs.1, Upsample1d ConvTranspose1d k4 after ups.0 / ups.1)
+        for (int k = 0; k < 12; ++k) {
+            const std::string pre = kBlocks[k].name;
+            const int cin = kBlocks[k].cin, c = kBlocks[k].cout;
             add(pre + ".time_mlp.1.weight", {c, 288}); add(pre + ".time_mlp.1.bias", {c});
             add(pre + ".blocks.0.block.0.weight", {c, cin, 5}); add(pre + ".blocks.0.block.0.bias", {c});
             add(pre + ".blocks.0.block.2.weight", {c}); add(pre + ".blocks.0.block.2.bias", {c});
             add(pre + ".blocks.1.block.0.weight", {c, c, 5}); add(pre + ".blocks.1.block.0.bias", {c});
             add(pre + ".blocks.1.block.2.weight", {c}); add(pre + ".blocks.1.block.2.bias", {c});
             if (cin != c) { add(pre + ".residual_conv.weight", {c, cin, 1}); add(pre + ".residual_conv.bias", {c}); }
-        };
-        add("model.time_mlp.1.weight", {128, 32}); add("model.time_mlp.1.bias", {128});
-        add("model.time_mlp.3.weight", {32, 128}); add("model.time_mlp.3.bias", {32});
-        const int dims[4] = {4, 64, 128, 256};
-        for (int i = 0; i < 3; ++i) {
-            const std::string pre = "model.downs." + std::to_string(i);
-            res(pre + ".0", dims[i], dims[i + 1]);
-            res(pre + ".1", dims[i + 1], dims[i + 1]);
-            if (i < 2) { add(pre + ".2.conv.weight", {dims[i + 1], dims[i + 1], 3}); add(pre + ".2.conv.bias", {dims[i + 1]}); }
-        }
-        res("model.mid_block1", 256, 256);
-        res("model.mid_block2", 256, 256);
-        for (int i = 0; i < 2; ++i) {
-            const std::string pre = "model.ups." + std::to_string(i);
-            const int co = dims[2 - i];
-            res(pre + ".0", 2 * dims[3 - i], co);
-            res(pre + ".1", co, co);
-            add(pre + ".2.conv.weight", {co, co, 4}); add(pre + ".2.conv.bias", {co});
+            const int ktap = (k == 1 || k == 3) ? 3 : (k == 9 || k == 11) ? 4 : 0;
+            if (ktap) {
+                const std::string lvl = pre.substr(0, pre.size() - 1) + "2.conv";
+                add(lvl + ".weight", {c, c, ktap}); add(lvl + ".bias", {c});
+            }
         }
         add("model.final_conv.0.block.0.weight", {64, 64, 5}); add("model.final_conv.0.block.0.bias", {64});
         add("model.final_conv.0.block.2.weight", {64}); add("model.final_conv.0.block.2.bias", {64});
         add("model.final_conv.1.weight", {4, 64, 1}); add("model.final_conv.1.bias", {4});
-        for (size_t i = 0; i < p.size(); ++i) p[i].name = names[i].c_str();
     }
-    size_t off(const std::string& n) const { return p[idx.at(n)].offset; }
 };
 
-const Table& table() {
-    static const Table t;
+const ParamTable& table() {
+    static const UnetTable t;
     return t;
 }
 
 // ------------------------------------------------------------------ the walk: tape layout and the launches
-struct BlockDef { const char* name; int cin, c, L; };
-const BlockDef kBlk[12] = {
-    {"model.downs.0.0", 4, 64, 52},    {"model.downs.0.1", 64, 64, 52},  {"model.downs.1.0", 64, 128, 26},
-    {"model.downs.1.1", 128, 128, 26}, {"model.downs.2.0", 128, 256, 13}, {"model.downs.2.1", 256, 256, 13},
-    {"model.mid_block1", 256, 256, 13}, {"model.mid_block2", 256, 256, 13}, {"model.ups.0.0", 512, 128, 13},
-    {"model.ups.0.1", 128, 128, 13},   {"model.ups.1.0", 256, 64, 26},   {"model.ups.1.1", 64, 64, 26},
-};
-
 // per-row floats of the tape items, in tape order; every item is a [B, ...] array
 struct Tape {
     size_t te0, a1, m1, tc, mt;
@@ -440,7 +409,7 @@ struct Tape {
         auto take = [&](size_t n) { const size_t r = o; o += n; return r; };
         te0 = take(32); a1 = take(128); m1 = take(128); tc = take(288); mt = take(288);
         for (int k = 0; k < 12; ++k) {
-            const size_t n = (size_t)kBlk[k].L * kBlk[k].c;
+            const size_t n = (size_t)kBlocks[k].L * kBlocks[k].cout;
             z0[k] = take(n); st0[k] = take(16); h1[k] = take(n); z1[k] = take(n); st1[k] = take(16); out[k] = take(n);
             if (k == 1) down[0] = take(26 * 64);
             if (k == 3) down[1] = take(13 * 128);
@@ -460,7 +429,7 @@ const Tape& tape_layout() {
 
 int cb_offset(int k) {
     int o = 0;
-    for (int i = 0; i < k; ++i) o += kBlk[i].c;
+    for (int i = 0; i < k; ++i) o += kBlocks[i].cout;
     return o;
 }
 
@@ -488,12 +457,24 @@ hipError_t gemm(const Ctx& c, const float* in, int lin, int cin, int in_ld, int 
     return hipGetLastError();
 }
 
+// The K split of a weight gradient and its two launches: at most max_chunks chunks of whole rows, the partials of chunk z at
+// part[z][M][N], summed in chunk order.  Fills a.rows_per and r.nchunk.
+hipError_t launch_wgrad(Wgrad a, WReduce r, int max_chunks, hipStream_t s) {
+    int nchunk = a.rows < max_chunks ? a.rows : max_chunks;
+    a.rows_per = (a.rows + nchunk - 1) / nchunk;
+    r.nchunk = (a.rows + a.rows_per - 1) / a.rows_per;
+    dim3 grid((a.N + BN - 1) / BN, (a.M + BM - 1) / BM, r.nchunk);
+    wgrad_kernel<<<grid, 256, 0, s>>>(a);
+    TRY(hipGetLastError());
+    wreduce_kernel<<<nblk((long)a.M * a.N), 256, 0, s>>>(r);
+    return hipGetLastError();
+}
+
 struct Bwd {
     Ctx c;
     float* dP;          // parameter gradients (null: data gradients only)
     int accumulate;
     float* part;
-    int rows_per, nchunk;
 };
 
 // weight gradient of (m, tap, c) -> dP[name_w][m om + c oc + tap ot], the ones column -> dP[name_b][m]
@@ -502,22 +483,11 @@ hipError_t wgrad(const Bwd& w, const float* P, int lp, int p_ld, int M, const fl
     if (!w.dP) return hipSuccess;
     const int N = (G ? ntap * gc : 0) + 1;
     if ((long)M * N > kPart) return hipErrorInvalidValue;
-    Wgrad a{P, lp, p_ld, M, G, lg, g_ld, G ? gc : 0, s, pd, G ? ntap : 0, w.c.B, w.rows_per, N, w.part};
-    dim3 grid((N + BN - 1) / BN, (M + BM - 1) / BM, w.nchunk);
-    wgrad_kernel<<<grid, 256, 0, w.c.s>>>(a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    WReduce r{w.part, w.nchunk, M, N, G ? gc : 0, G ? ntap : 0, name_w ? w.dP + table().off(name_w) : nullptr, om, oc, ot,
-              name_b ? w.dP + table().off(name_b) : nullptr, w.accumulate};
-    wreduce_kernel<<<nblk((long)M * N), 256, 0, w.c.s>>>(r);
-    return hipGetLastError();
+    const Wgrad a{P, lp, p_ld, M, G, lg, g_ld, G ? gc : 0, s, pd, G ? ntap : 0, w.c.B, 0, N, w.part};
+    const WReduce r{w.part, 0, M, N, a.gc, a.ntap, name_w ? w.dP + table().off(name_w) : nullptr, om, oc, ot,
+                    name_b ? w.dP + table().off(name_b) : nullptr, w.accumulate, nullptr};
+    return launch_wgrad(a, r, kChunks, w.c.s);
 }
-
-#define TRY(expr)                                  \
-    do {                                           \
-        hipError_t e__ = (expr);                   \
-        if (e__ != hipSuccess) return e__;         \
-    } while (0)
 
 // workspace: packed weights | per-block bias rows [B, 1792] | residual scratch [B, 3328]  (forward)
 //            packed weights | partials | dA, dB [B, 6656] | T1, dZ, dskip1, dskip2 [B, 3328] | rows ...  (backward)
@@ -565,7 +535,7 @@ hipError_t train_forward(const float* params, const float* x, const float* cond,
     // pack every weight as the forward GEMMs read it: [tap][c_in][c_out]
     for (int i = 0; i < kTrainParams; ++i) {
         const TrainParam& p = table().p[i];
-        const std::string n = table().names[i];
+        const std::string n = p.name;
         if (p.ndim == 1) continue;
         if (p.ndim == 2) TRY(pack(c, n, 1, p.shape[1], p.shape[0], 0, 1, p.shape[1]));                  // Linear [out, in]
         else if (n.find(".conv.weight") != std::string::npos && n.rfind("model.ups.", 0) == 0)
@@ -587,14 +557,14 @@ hipError_t train_forward(const float* params, const float* x, const float* cond,
     tc_fwd_kernel<<<nblk(B * 288), 256, 0, s>>>(tp(T.tc), cond, tp(T.mt), B);
     TRY(hipGetLastError());
     for (int k = 0; k < 12; ++k) {
-        const std::string pre = kBlk[k].name;
+        const std::string pre = kBlocks[k].name;
         TRY(gemm(c, tp(T.mt), 1, 288, 288, 0, 1, 0, 1, c.pk(pre + ".time_mlp.1.weight"), c.prm(pre + ".time_mlp.1.bias"), tbs + cb_offset(k), 1,
-                 kBlk[k].c, NCB, 0));
+                 kBlocks[k].cout, NCB, 0));
     }
     // residual blocks: out = Mish(GN(conv(Mish(GN(conv x)) + tb))) + res(x)
     auto block = [&](int k, const float* xin) -> hipError_t {
-        const std::string pre = kBlk[k].name;
-        const int L = kBlk[k].L, cin = kBlk[k].cin, C = kBlk[k].c;
+        const std::string pre = kBlocks[k].name;
+        const int L = kBlocks[k].L, cin = kBlocks[k].cin, C = kBlocks[k].cout;
         TRY(gemm(c, xin, L, cin, cin, 0, 1, 2, 5, c.pk(pre + ".blocks.0.block.0.weight"), c.prm(pre + ".blocks.0.block.0.bias"), tp(T.z0[k]), L, C, C, 0));
         GnFwd g0{tp(T.z0[k]), tp(T.h1[k]), tp(T.st0[k]), c.prm(pre + ".blocks.0.block.2.weight"), c.prm(pre + ".blocks.0.block.2.bias"),
                  tbs + cb_offset(k), NCB, nullptr, L, C};
@@ -646,17 +616,14 @@ hipError_t train_backward(const float* params, const float* x, const float* tape
                           float* dcond, int accumulate, int B, float* ws, hipStream_t s) {
     const Tape& T = tape_layout();
     WsB w = carve_bwd(ws, B);
-    Bwd g{Ctx{params, w.wp, B, s}, d_params, accumulate, w.part, 0, 0};
-    g.nchunk = B < kChunks ? B : kChunks;
-    g.rows_per = (B + g.nchunk - 1) / g.nchunk;
-    g.nchunk = (B + g.rows_per - 1) / g.rows_per;
+    const Bwd g{Ctx{params, w.wp, B, s}, d_params, accumulate, w.part};
     const Ctx& c = g.c;
     float* tape = const_cast<float*>(tape_c);
     auto tp = [&](size_t off) { return tape + off * (size_t)B; };
     // pack every weight as the data-gradient GEMMs read it: [tap][c_out][c_in] (the adjoint's reduction runs over c_out)
     for (int i = 0; i < kTrainParams; ++i) {
         const TrainParam& p = table().p[i];
-        const std::string n = table().names[i];
+        const std::string n = p.name;
         if (p.ndim == 1) continue;
         if (p.ndim == 2) TRY(pack(c, n, 1, p.shape[0], p.shape[1], 0, p.shape[1], 1));                  // Linear [out, in]
         else if (n.find(".conv.weight") != std::string::npos && n.rfind("model.ups.", 0) == 0)
@@ -679,8 +646,8 @@ hipError_t train_backward(const float* params, const float* x, const float* tape
     bool first_tb = true;
     // residual block k: d_out -> d_xin (written)
     auto block = [&](int k, const float* xin, const float* d_out, float* d_xin) -> hipError_t {
-        const std::string pre = kBlk[k].name;
-        const int L = kBlk[k].L, cin = kBlk[k].cin, C = kBlk[k].c;
+        const std::string pre = kBlocks[k].name;
+        const int L = kBlocks[k].L, cin = kBlocks[k].cin, C = kBlocks[k].cout;
         TRY(gnb(d_out, tp(T.z1[k]), tp(T.st1[k]), pre + ".blocks.1.block.2", w.dZ, nullptr, L, C));
         TRY(conv_bwd(pre + ".blocks.1.block.0", tp(T.h1[k]), L, C, w.dZ, L, C, 5, 1, 2, w.T1, 0));
         TRY(gnb(w.T1, tp(T.z0[k]), tp(T.st0[k]), pre + ".blocks.0.block.2", w.dZ, w.dsum, L, C));
@@ -758,17 +725,10 @@ size_t train_wgrad_part_floats(int M, int gc) { return (size_t)kWgradChunks * M 
 
 hipError_t train_wgrad(const float* P, int lp, int p_ld, int M, const float* G, int lg, int g_ld, int gc, int pd, int rows, float* dw,
                        long om, float* db, float* db2, int accumulate, float* part, hipStream_t s) {
-    int nchunk = rows < kWgradChunks ? rows : kWgradChunks;
-    const int rows_per = (rows + nchunk - 1) / nchunk;
-    nchunk = (rows + rows_per - 1) / rows_per;
     const int N = gc + 1;
-    Wgrad a{P, lp, p_ld, M, G, lg, g_ld, gc, 1, pd, 1, rows, rows_per, N, part};
-    dim3 grid((N + BN - 1) / BN, (M + BM - 1) / BM, nchunk);
-    wgrad_kernel<<<grid, 256, 0, s>>>(a);
-    TRY(hipGetLastError());
-    WReduce r{part, nchunk, M, N, gc, 1, dw, om, 1, 0, db, accumulate, db2};
-    wreduce_kernel<<<nblk((long)M * N), 256, 0, s>>>(r);
-    return hipGetLastError();
+    const Wgrad a{P, lp, p_ld, M, G, lg, g_ld, gc, 1, pd, 1, rows, 0, N, part};
+    const WReduce r{part, 0, M, N, gc, 1, dw, om, 1, 0, db, accumulate, db2};
+    return launch_wgrad(a, r, kWgradChunks, s);
 }
 
 }  // namespace cld

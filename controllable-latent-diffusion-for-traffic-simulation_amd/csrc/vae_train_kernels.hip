@@ -15,9 +15,7 @@
 // path's weight-gradient GEMM (train_wgrad: K split over whole rows, summed in a fixed order, no float atomics).
 #include <hip/hip_runtime.h>
 
-#include <map>
 #include <string>
-#include <vector>
 
 #include "train.h"
 
@@ -31,24 +29,8 @@ constexpr int T = 52, H = 64, G4 = 256, AG = 16, COND = 256;
 __device__ __forceinline__ float sigm(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 // ------------------------------------------------------------------ parameter table (LSTMVAE state_dict order)
-struct Table {
-    std::vector<TrainParam> p;
-    std::vector<std::string> names;
-    std::map<std::string, int> idx;
-    size_t floats = 0;
-    Table() {
-        auto add = [&](const std::string& n, std::vector<int> shape) {
-            TrainParam t{};
-            size_t numel = 1;
-            for (size_t i = 0; i < shape.size(); ++i) { t.shape[i] = shape[i]; numel *= shape[i]; }
-            t.ndim = (int)shape.size();
-            t.numel = numel;
-            t.offset = floats;
-            floats += (numel + kTrainAlign - 1) / kTrainAlign * kTrainAlign;
-            idx[n] = (int)p.size();
-            names.push_back(n);
-            p.push_back(t);
-        };
+struct VaeTable : ParamTable {
+    VaeTable() {
         auto stack = [&](const std::string& pre, int in) {      // lstm_vae.py:6-19 / 28-43
             add(pre + ".lstm.weight_ih_l0", {G4, in}); add(pre + ".lstm.weight_hh_l0", {G4, H});
             add(pre + ".lstm.bias_ih_l0", {G4});       add(pre + ".lstm.bias_hh_l0", {G4});
@@ -61,13 +43,11 @@ struct Table {
         add("lstm_dec.hid2act.weight", {2, H}); add("lstm_dec.hid2act.bias", {2});
         add("mu.weight", {4, H});     add("mu.bias", {4});          // lstm_vae.py:79-80
         add("logvar.weight", {4, H}); add("logvar.bias", {4});
-        for (size_t i = 0; i < p.size(); ++i) p[i].name = names[i].c_str();
     }
-    size_t off(const std::string& n) const { return p[idx.at(n)].offset; }
 };
 
-const Table& table() {
-    static const Table t;
+const ParamTable& table() {
+    static const VaeTable t;
     return t;
 }
 
@@ -415,14 +395,6 @@ __global__ __launch_bounds__(256) void dcond_kernel(const float* __restrict__ wc
     for (int u = 0; u < H; ++u) s = fmaf(dh0[(size_t)b * H + u], wc[u * COND + k], s);
     dcond[idx] = s;
 }
-
-inline unsigned nblk(long n) { return (unsigned)((n + 255) / 256); }
-
-#define TRY(expr)                                  \
-    do {                                           \
-        hipError_t e__ = (expr);                   \
-        if (e__ != hipSuccess) return e__;         \
-    } while (0)
 
 // workspace of the backward: dgates of both layers | the heads' cotangent | dh0 | zeros (a null head cotangent) | weight-gradient partials
 struct Ws {

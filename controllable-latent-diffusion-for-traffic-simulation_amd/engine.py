@@ -93,8 +93,8 @@ class Engine:
             rc = self.lib.cld_create(C.byref(cfg), C.byref(self._h))
         if rc != 0:
             raise CldError(f"cld_create failed ({rc})")
-        self._ws = None
-        self._ctx_ws = None
+        self._ws = self._ctx_ws = self._tws = self._vws = None      # grow-only device scratch (_scratch): sampling, ContextEncoder,
+                                                                    # U-Net training, VAE training
         self._nc_map_feat = {}
         self._finalized = False
         self.precision = {v: k for k, v in _lib.PRECISIONS.items()}[int(self.lib.cld_get_precision(self._h))]
@@ -110,11 +110,16 @@ class Engine:
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
+    def _scratch(self, slot: str, nbytes: int):
+        """(pointer, size) of the scratch buffer kept in attribute `slot`, reallocated only when `nbytes` exceeds its size."""
+        buf = getattr(self, slot)
+        if buf is None or buf.numel() < nbytes:
+            buf = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            setattr(self, slot, buf)
+        return C.c_void_p(buf.data_ptr()), C.c_size_t(buf.numel())
+
     def _workspace(self, B: int):
-        need = int(self.lib.cld_workspace_bytes(self._h, B))
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        return C.c_void_p(self._ws.data_ptr()), C.c_size_t(self._ws.numel())
+        return self._scratch("_ws", int(self.lib.cld_workspace_bytes(self._h, B)))
 
     def _f32(self, t: torch.Tensor, shape=None) -> torch.Tensor:
         if not isinstance(t, torch.Tensor):
@@ -615,12 +620,6 @@ class Engine:
         """[(name, offset, numel, shape)] of the 148 U-Net tensors in the flat parameter buffer, and the buffer's length in floats."""
         return unet_param_table(self.lib, self._h)
 
-    def _train_workspace(self, B: int):
-        need = int(self.lib.cld_unet_train_workspace_bytes(self._h, B))
-        if getattr(self, "_tws", None) is None or self._tws.numel() < need:
-            self._tws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        return C.c_void_p(self._tws.data_ptr()), C.c_size_t(self._tws.numel())
-
     def unet_train_forward(self, params, x, cond, t):
         """eps [B,52,4] of the U-Net with the weights of `params` (flat fp32 device buffer, `unet_param_table` layout) and one
         timestep per row, plus the tape `unet_backward` needs (a uint8 device tensor)."""
@@ -630,7 +629,7 @@ class Engine:
         t = self._timesteps(t, B)
         eps = torch.empty_like(x)
         tape = torch.empty(int(self.lib.cld_unet_tape_bytes(self._h, B)), dtype=torch.uint8, device=self.device)
-        ws, wsn = self._train_workspace(B)
+        ws, wsn = self._scratch("_tws", int(self.lib.cld_unet_train_workspace_bytes(self._h, B)))
         with torch.cuda.device(self.device):
             self._check(self.lib.cld_unet_train_forward(self._h, _ptr(params), _ptr(x), _ptr(cond), _ptr(t), _ptr(eps), _ptr(tape),
                                                         tape.numel(), B, ws, wsn, self._stream()), "cld_unet_train_forward")
@@ -646,7 +645,7 @@ class Engine:
         t = self._timesteps(t, B)
         dx = torch.empty_like(x) if want_dx else None
         dcond = torch.empty_like(cond) if want_dcond else None
-        ws, wsn = self._train_workspace(B)
+        ws, wsn = self._scratch("_tws", int(self.lib.cld_unet_train_workspace_bytes(self._h, B)))
         with torch.cuda.device(self.device):
             self._check(self.lib.cld_unet_backward(self._h, _ptr(params), _ptr(x), _ptr(cond), _ptr(t), _ptr(tape), tape.numel(),
                                                    _ptr(d_eps), _ptr(d_params), _ptr(dx), _ptr(dcond), int(bool(accumulate)), B,
@@ -657,12 +656,6 @@ class Engine:
     def vae_param_table(self):
         """[(name, offset, numel, shape)] of the 26 LSTMVAE tensors in the flat parameter buffer, and the buffer's length in floats."""
         return vae_param_table(self.lib, self._h)
-
-    def _vae_workspace(self, B: int):
-        need = int(self.lib.cld_vae_train_workspace_bytes(self._h, B))
-        if getattr(self, "_vws", None) is None or self._vws.numel() < need:
-            self._vws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        return C.c_void_p(self._vws.data_ptr()), C.c_size_t(self._vws.numel())
 
     def _vae_args(self, x, width, cond, mask):
         x = self._f32(x)
@@ -691,7 +684,7 @@ class Engine:
         d_logvar = None if d_logvar is None else self._f32(d_logvar, (B, T, D))
         dx = torch.empty_like(x) if want_dx else None
         dcond = torch.empty_like(cond) if want_dcond else None
-        ws, wsn = self._vae_workspace(B)
+        ws, wsn = self._scratch("_vws", int(self.lib.cld_vae_train_workspace_bytes(self._h, B)))
         with torch.cuda.device(self.device):
             self._check(self.lib.cld_vae_encode_backward(self._h, _ptr(params), _ptr(x), _ptr(cond), _ptr(mask), _ptr(tape), tape.numel(),
                                                          _ptr(d_mu), _ptr(d_logvar), _ptr(d_params), _ptr(dx), _ptr(dcond),
@@ -714,7 +707,7 @@ class Engine:
         d_act = self._f32(d_act, (B, T, 2))
         dz = torch.empty_like(z) if want_dz else None
         dcond = torch.empty_like(cond) if want_dcond else None
-        ws, wsn = self._vae_workspace(B)
+        ws, wsn = self._scratch("_vws", int(self.lib.cld_vae_train_workspace_bytes(self._h, B)))
         with torch.cuda.device(self.device):
             self._check(self.lib.cld_vae_decode_backward(self._h, _ptr(params), _ptr(z), _ptr(cond), _ptr(mask), _ptr(tape), tape.numel(),
                                                          _ptr(d_act), _ptr(d_params), _ptr(dz), _ptr(dcond), int(bool(accumulate)), B,
@@ -806,13 +799,10 @@ class Engine:
         image = self._f32(image, (B, 34, 224, 224)); cs = self._f32(curr_states, (B, 4))
         cond = torch.empty(B, COND, dtype=torch.float32, device=self.device)
         mf = torch.empty(B, 256, dtype=torch.float32, device=self.device) if want_map_feat else None
-        need = int(self.lib.cld_context_workspace_bytes(self._h, B))
-        if self._ctx_ws is None or self._ctx_ws.numel() < need:
-            self._ctx_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        ws, wsn = self._scratch("_ctx_ws", int(self.lib.cld_context_workspace_bytes(self._h, B)))
         with torch.cuda.device(self.device):
             self._check(self.lib.cld_context_encode(self._h, _ptr(image), _ptr(cs), _ptr(cond), _ptr(mf), B,
-                                                    C.c_void_p(self._ctx_ws.data_ptr()), C.c_size_t(self._ctx_ws.numel()),
-                                                    self._stream()), "cld_context_encode")
+                                                    ws, wsn, self._stream()), "cld_context_encode")
         return (cond, mf) if want_map_feat else cond
 
     def non_cond_feat(self, curr_states, cond_fill_value: float = -1.0):

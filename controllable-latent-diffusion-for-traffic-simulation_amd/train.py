@@ -24,76 +24,53 @@ from .engine import Engine, unet_param_table
 from .vae_model import VaeModel
 
 
+def _keep(ctx, engine: Engine, flat, table, tape, mask, *inputs):
+    """What every forward below leaves for its backward: the engine, the flat buffer and the (name, offset, numel, shape) entries of
+    `params`, the tape, the dropout mask (None: none) and the detached inputs."""
+    ctx.engine, ctx.flat, ctx.table, ctx.tape, ctx.mask = engine, flat, table, tape, mask
+    ctx.save_for_backward(*inputs)
+
+
+def _backward(ctx, new_d_flat, engine_backward):
+    """The tail the three backwards share.  `new_d_flat(flat)` allocates the flat gradient buffer when a parameter needs one,
+    `engine_backward(d_flat, want_dx, want_dcond)` runs the engine's backward and returns (dx, dcond).  Releases the tape and returns
+    the gradients of (x, cond, third input, engine, flat, table, *params): d_flat sliced by the table for the parameters."""
+    want_dp = any(ctx.needs_input_grad[6:])
+    d_flat = new_d_flat(ctx.flat) if want_dp else None
+    dx, dcond = engine_backward(d_flat, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+    ctx.tape = None
+    grads = [d_flat[off:off + n].view(shape) for (_, off, n, shape) in ctx.table] if want_dp else [None] * len(ctx.table)
+    return (dx, dcond, None, None, None, None, *grads)
+
+
 class UnetFn(torch.autograd.Function):
     """eps = U-Net(x, cond, t) with the weights of `flat`; `params` are the views of `flat` that receive the gradients."""
 
     @staticmethod
     def forward(ctx, x, cond, t, engine: Engine, flat, table, *params):
         eps, tape = engine.unet_train_forward(flat, x, cond, t)
-        ctx.engine, ctx.table, ctx.flat = engine, table, flat
-        ctx.save_for_backward(x.detach(), cond.detach(), torch.as_tensor(t))
-        ctx.tape = tape
+        _keep(ctx, engine, flat, table, tape, None, x.detach(), cond.detach(), torch.as_tensor(t))
         return eps
 
     @staticmethod
     def backward(ctx, d_eps):
         x, cond, t = ctx.saved_tensors
-        want_dx, want_dcond = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        want_dp = any(ctx.needs_input_grad[6:])
-        d_flat = torch.zeros_like(ctx.flat) if want_dp else None
-        dx, dcond = ctx.engine.unet_backward(ctx.flat, x, cond, t, ctx.tape, d_eps.contiguous(), d_params=d_flat,
-                                             want_dx=want_dx, want_dcond=want_dcond)
-        ctx.tape = None
-        grads = [None] * len(ctx.table)
-        if want_dp:
-            grads = [d_flat[off:off + n].view(shape) for (_, off, n, shape) in ctx.table]
-        return (dx, dcond, None, None, None, None, *grads)
+        return _backward(ctx, torch.zeros_like, lambda d_flat, want_dx, want_dcond: ctx.engine.unet_backward(
+            ctx.flat, x, cond, t, ctx.tape, d_eps.contiguous(), d_params=d_flat, want_dx=want_dx, want_dcond=want_dcond))
 
 
-def _strip(k: str) -> str:
-    return k[3:] if k.startswith("dm.") else k
+class _FlatParams:
+    """The parameter surface of an nn.Module over ONE flat fp32 device tensor: `nn.Parameter` views of it under the reference's
+    state_dict names.  A subclass sets `_strip` (a key of a caller's state_dict -> the reference name) and `_KEYS` (the prefixes of
+    this model's names: an unknown key under one of them is an error of a strict load, any other key is ignored)."""
 
-
-class _UnetModel:
-    """`dm.model(x, aux_info, t)` (TemporalMapUnet.forward, temporal.py:122-180), differentiable."""
-
-    def __init__(self, dm: "TrainableDm"):
-        self._dm = dm
-
-    def __call__(self, x, aux_info, time):
-        return self._dm._unet(x, aux_info["cond_feat"], time)
-
-
-class TrainableDm:
-    """A trainable DmModel (models/dm/dm_model.py:15-174) over the HIP training path.
-
-    `weights`: the U-Net state_dict ("model.*" keys, optional "dm." prefix).  `parameters()` / `named_parameters()` /
-    `state_dict()` / `load_state_dict()` follow the reference names; `model(x, aux_info, t)`, `compute_losses(aux_info, z0,
-    t=None, noise=None)` and `log_prob(x_t, x_tm1, aux_info, t)` are differentiable with respect to the parameters (and to x /
-    cond where those require grad).  `to_engine()` gives a finalized DmModel with the current weights for sampling."""
-
-    def __init__(self, weights: Mapping, n_timesteps: int = 100, device="cuda:0"):
-        self.n_timesteps = int(n_timesteps)
-        self.device = torch.device(device)
-        self.engine = Engine(n_timesteps=self.n_timesteps, device=device)
-        sd = {_strip(k): v for k, v in weights.items() if _strip(k).startswith("model.")}
-        self.engine.load_state_dict(sd).finalize()     # the training calls need a finalized exact-fp32 U-Net handle
-        self._table, nflat = self.engine.unet_param_table()
+    def _init_params(self, table, nflat: int):
         self._flat = torch.zeros(nflat, dtype=torch.float32, device=self.device)
-        self._params = {}
-        for name, off, n, shape in self._table:
-            p = torch.nn.Parameter(self._flat[off:off + n].view(shape))
-            self._params[name] = p
-        self.load_state_dict(sd)
-        self.model = _UnetModel(self)
-        f = lambda a: torch.from_numpy(a).to(self.device)       # noqa: E731
-        self.x_t_cof, self.noise_cof = f(self.engine.x_t_cof), f(self.engine.noise_cof)
-        self.posterior_log_variance_clipped = f(self.engine.posterior_log_variance_clipped)
+        self._params = {name: torch.nn.Parameter(self._flat[off:off + n].view(shape)) for name, off, n, shape in table}
 
-    # ------------------------------------------------------------------ parameters
     @property
     def flat(self) -> torch.Tensor:
-        """The flat fp32 device buffer the parameters are views of (cld_unet_param_info layout)."""
+        """The flat fp32 device buffer the parameters are views of (cld_unet_param_info / cld_vae_param_info layout)."""
         return self._flat
 
     def named_parameters(self):
@@ -106,9 +83,9 @@ class TrainableDm:
         return {k: p.detach().clone() for k, p in self._params.items()}
 
     def load_state_dict(self, sd: Mapping, strict: bool = True):
-        sd = {_strip(k): v for k, v in sd.items()}
+        sd = {self._strip(k): v for k, v in sd.items()}
         missing = [k for k in self._params if k not in sd]
-        unknown = [k for k in sd if k not in self._params and k.startswith("model.")]
+        unknown = [k for k in sd if k not in self._params and k.startswith(self._KEYS)]
         if strict and (missing or unknown):
             raise CldError(f"load_state_dict: missing {missing[:4]}, unknown {unknown[:4]}")
         with torch.no_grad():
@@ -126,6 +103,45 @@ class TrainableDm:
                 p.grad = None
             elif p.grad is not None:
                 p.grad.zero_()
+
+
+def _strip_dm(k: str) -> str:
+    return k[3:] if k.startswith("dm.") else k
+
+
+class _UnetModel:
+    """`dm.model(x, aux_info, t)` (TemporalMapUnet.forward, temporal.py:122-180), differentiable."""
+
+    def __init__(self, dm: "TrainableDm"):
+        self._dm = dm
+
+    def __call__(self, x, aux_info, time):
+        return self._dm._unet(x, aux_info["cond_feat"], time)
+
+
+class TrainableDm(_FlatParams):
+    """A trainable DmModel (models/dm/dm_model.py:15-174) over the HIP training path.
+
+    `weights`: the U-Net state_dict ("model.*" keys, optional "dm." prefix).  `parameters()` / `named_parameters()` /
+    `state_dict()` / `load_state_dict()` follow the reference names; `model(x, aux_info, t)`, `compute_losses(aux_info, z0,
+    t=None, noise=None)` and `log_prob(x_t, x_tm1, aux_info, t)` are differentiable with respect to the parameters (and to x /
+    cond where those require grad).  `to_engine()` gives a finalized DmModel with the current weights for sampling."""
+
+    _strip, _KEYS = staticmethod(_strip_dm), ("model.",)
+
+    def __init__(self, weights: Mapping, n_timesteps: int = 100, device="cuda:0"):
+        self.n_timesteps = int(n_timesteps)
+        self.device = torch.device(device)
+        self.engine = Engine(n_timesteps=self.n_timesteps, device=device)
+        sd = {_strip_dm(k): v for k, v in weights.items() if _strip_dm(k).startswith("model.")}
+        self.engine.load_state_dict(sd).finalize()     # the training calls need a finalized exact-fp32 U-Net handle
+        self._table, nflat = self.engine.unet_param_table()
+        self._init_params(self._table, nflat)
+        self.load_state_dict(sd)
+        self.model = _UnetModel(self)
+        f = lambda a: torch.from_numpy(a).to(self.device)       # noqa: E731
+        self.x_t_cof, self.noise_cof = f(self.engine.x_t_cof), f(self.engine.noise_cof)
+        self.posterior_log_variance_clipped = f(self.engine.posterior_log_variance_clipped)
 
     # ------------------------------------------------------------------ the U-Net and the loss heads
     def _timesteps(self, t, B: int) -> torch.Tensor:
@@ -187,21 +203,16 @@ class VaeEncodeFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, cond, mask, engine: Engine, flat, table, *params):
         mu, lv, tape = engine.vae_encode_train(flat, x, cond, mask)
-        ctx.engine, ctx.table, ctx.flat, ctx.mask, ctx.tape = engine, table, flat, mask, tape
-        ctx.save_for_backward(x.detach(), cond.detach())
+        _keep(ctx, engine, flat, table, tape, mask, x.detach(), cond.detach())
         return mu, lv
 
     @staticmethod
     def backward(ctx, d_mu, d_lv):
         x, cond = ctx.saved_tensors
-        want_dp = any(ctx.needs_input_grad[6:])
-        d_flat = torch.empty_like(ctx.flat) if want_dp else None     # accumulate=0 writes every tensor of the encoder
-        dx, dcond = ctx.engine.vae_encode_backward(ctx.flat, x, cond, ctx.mask, ctx.tape,
-                                                   None if d_mu is None else d_mu.contiguous(), None if d_lv is None else d_lv.contiguous(),
-                                                   d_params=d_flat, want_dx=ctx.needs_input_grad[0], want_dcond=ctx.needs_input_grad[1])
-        ctx.tape = None
-        grads = [d_flat[off:off + n].view(shape) for (_, off, n, shape) in ctx.table] if want_dp else [None] * len(ctx.table)
-        return (dx, dcond, None, None, None, None, *grads)
+        d_mu, d_lv = (None if d is None else d.contiguous() for d in (d_mu, d_lv))
+        # empty_like: accumulate=0 writes every tensor of the encoder
+        return _backward(ctx, torch.empty_like, lambda d_flat, want_dx, want_dcond: ctx.engine.vae_encode_backward(
+            ctx.flat, x, cond, ctx.mask, ctx.tape, d_mu, d_lv, d_params=d_flat, want_dx=want_dx, want_dcond=want_dcond))
 
 
 class VaeDecodeFn(torch.autograd.Function):
@@ -210,20 +221,15 @@ class VaeDecodeFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, z, cond, mask, engine: Engine, flat, table, *params):
         act, tape = engine.vae_decode_train(flat, z, cond, mask)
-        ctx.engine, ctx.table, ctx.flat, ctx.mask, ctx.tape = engine, table, flat, mask, tape
-        ctx.save_for_backward(z.detach(), cond.detach())
+        _keep(ctx, engine, flat, table, tape, mask, z.detach(), cond.detach())
         return act
 
     @staticmethod
     def backward(ctx, d_act):
         z, cond = ctx.saved_tensors
-        want_dp = any(ctx.needs_input_grad[6:])
-        d_flat = torch.empty_like(ctx.flat) if want_dp else None
-        dz, dcond = ctx.engine.vae_decode_backward(ctx.flat, z, cond, ctx.mask, ctx.tape, d_act.contiguous(), d_params=d_flat,
-                                                   want_dz=ctx.needs_input_grad[0], want_dcond=ctx.needs_input_grad[1])
-        ctx.tape = None
-        grads = [d_flat[off:off + n].view(shape) for (_, off, n, shape) in ctx.table] if want_dp else [None] * len(ctx.table)
-        return (dz, dcond, None, None, None, None, *grads)
+        # empty_like: accumulate=0 writes every tensor of the decoder
+        return _backward(ctx, torch.empty_like, lambda d_flat, want_dz, want_dcond: ctx.engine.vae_decode_backward(
+            ctx.flat, z, cond, ctx.mask, ctx.tape, d_act.contiguous(), d_params=d_flat, want_dz=want_dz, want_dcond=want_dcond))
 
 
 _VAE_KEYS = ("lstm_enc.", "lstm_dec.", "mu.", "logvar.")
@@ -236,7 +242,7 @@ def _strip_vae(k: str) -> str:
     return k
 
 
-class TrainableVae:
+class TrainableVae(_FlatParams):
     """A trainable LSTMVAE (models/vae/lstm_vae.py:54-99) over the HIP training path, with VaeModel.compute_vae_loss.
 
     `weights`: the LSTMVAE state_dict ('lstmvae.' / 'vae.lstmvae.' prefixes stripped; other keys, e.g. 'context_encoder.*', ignored).
@@ -246,57 +252,22 @@ class TrainableVae:
     and `forward` are differentiable with respect to the parameters and to x / z / context where those require grad (the encoder's and
     the decoder's dcond add).  `to_vae_model()` gives a finalized VaeModel with the current weights for the sampling path."""
 
+    _strip, _KEYS = staticmethod(_strip_vae), _VAE_KEYS
+
     def __init__(self, weights: Mapping, device="cuda:0", dropout: float = 0.2):
         self.device = torch.device(device)
         self.p = float(dropout)
         self.training = True
         self.engine = Engine(device=device)       # the training calls read every weight from the flat buffer: no weights, no finalize
         table, nflat = self.engine.vae_param_table()
-        self._flat = torch.zeros(nflat, dtype=torch.float32, device=self.device)
-        self._params = {name: torch.nn.Parameter(self._flat[off:off + n].view(shape)) for name, off, n, shape in table}
+        self._init_params(table, nflat)
         enc = [e for e in table if not e[0].startswith("lstm_dec.")]
         dec = [e for e in table if e[0].startswith("lstm_dec.")]
         self._enc = (enc, [self._params[e[0]] for e in enc])
         self._dec = (dec, [self._params[e[0]] for e in dec])
         self.load_state_dict(weights)
 
-    # ------------------------------------------------------------------ parameters and mode
-    @property
-    def flat(self) -> torch.Tensor:
-        """The flat fp32 device buffer the parameters are views of (cld_vae_param_info layout)."""
-        return self._flat
-
-    def named_parameters(self):
-        return iter(self._params.items())
-
-    def parameters(self):
-        return iter(self._params.values())
-
-    def state_dict(self) -> dict:
-        return {k: p.detach().clone() for k, p in self._params.items()}
-
-    def load_state_dict(self, sd: Mapping, strict: bool = True):
-        sd = {_strip_vae(k): v for k, v in sd.items()}
-        missing = [k for k in self._params if k not in sd]
-        unknown = [k for k in sd if k not in self._params and k.startswith(_VAE_KEYS)]
-        if strict and (missing or unknown):
-            raise CldError(f"load_state_dict: missing {missing[:4]}, unknown {unknown[:4]}")
-        with torch.no_grad():
-            for k, p in self._params.items():
-                if k in sd:
-                    v = torch.as_tensor(sd[k]).to(device=self.device, dtype=torch.float32)
-                    if tuple(v.shape) != tuple(p.shape):
-                        raise CldError(f"load_state_dict: '{k}' expects shape {tuple(p.shape)}, got {tuple(v.shape)}")
-                    p.copy_(v)
-        return self
-
-    def zero_grad(self, set_to_none: bool = True):
-        for p in self._params.values():
-            if set_to_none:
-                p.grad = None
-            elif p.grad is not None:
-                p.grad.zero_()
-
+    # ------------------------------------------------------------------ mode
     def train(self, mode: bool = True):
         self.training = bool(mode)
         return self

@@ -8,12 +8,11 @@ The ratios (left side over the bar) are printed with -s.  Batch sizes 1, 5, 37, 
 timesteps spread over 0..99 with 0 and 99 included.  In the f16x2 parametrisation the library refuses the training calls, which is
 asserted; the rest of the module is skipped there.
 """
-import math
-
 import numpy as np
 import pytest
 import torch
 
+import grad_bar
 from cld_amd import _lib, synth
 from cld_amd.engine import Engine
 from oracle import cld_oracle as O
@@ -66,24 +65,8 @@ def _oracle_grads(weights, x, cond, t, d_eps, dtype):
     return eps.detach(), g
 
 
-def _ratio(g, g64, g32):
-    g, g64, g32 = (torch.as_tensor(a).double().cpu() for a in (g, g64, g32))
-    bar = 4 * (g32 - g64).abs().max() + 1e-7 * g64.abs().max()
-    err = float((g - g64).abs().max())
-    return err / float(bar) if bar > 0 else (0.0 if err == 0 else math.inf)
-
-
 def _check_all(tag, got, g64, g32):
-    worst = (0.0, None)
-    bad = []
-    for k in g64:
-        r = _ratio(got[k], g64[k], g32[k])
-        worst = max(worst, (r, k), key=lambda a: a[0])
-        if not r <= 1.0:
-            bad.append((k, r))
-    _RATIOS[tag] = worst
-    print(f"\n[train] {tag}: worst ratio {worst[0]:.3g} ({worst[1]}), {len(g64)} tensors")
-    assert not bad, f"{tag}: over the bar: {bad[:6]}"
+    grad_bar.check_all("train", _RATIOS, tag, got, g64, g32)
 
 
 def _gpu_grads(dm, x, cond, t, d_eps):

@@ -11,12 +11,11 @@ whole group, a whole group and one row, three groups, and many groups whose weig
 train_kernels.hip train_wgrad) has chunks of two rows and a ragged last chunk of one.  Inputs are scaled so that some gates saturate.
 In the f16x2 parametrisation the library refuses the training calls, which is asserted; the rest of the module is skipped there.
 """
-import math
-
 import numpy as np
 import pytest
 import torch
 
+import grad_bar
 import vae_yardstick as Y
 from cld_amd import _lib, synth
 from cld_amd.engine import Engine
@@ -83,24 +82,8 @@ def _gpu_grads(vae, x6, z, cond, cot, masks):
     return (mu.detach().cpu(), lv.detach().cpu(), act.detach().cpu()), g
 
 
-def _ratio(g, g64, g32):
-    g, g64, g32 = (torch.as_tensor(a).double().cpu() for a in (g, g64, g32))
-    bar = 4 * (g32 - g64).abs().max() + 1e-7 * g64.abs().max()
-    err = float((g - g64).abs().max())
-    return err / float(bar) if bar > 0 else (0.0 if err == 0 else math.inf)
-
-
 def _check_all(tag, got, g64, g32):
-    worst = (0.0, None)
-    bad = []
-    for k in g64:
-        r = _ratio(got[k], g64[k], g32[k])
-        worst = max(worst, (r, k), key=lambda a: a[0])
-        if not r <= 1.0:
-            bad.append((k, r))
-    _RATIOS[tag] = worst
-    print(f"\n[vae train] {tag}: worst ratio {worst[0]:.3g} ({worst[1]}), {len(g64)} tensors")
-    assert not bad, f"{tag}: over the bar: {bad[:6]}"
+    grad_bar.check_all("vae train", _RATIOS, tag, got, g64, g32)
 
 
 @pytest.mark.parametrize("masked", [False, True], ids=["eval", "dropout"])
