@@ -86,6 +86,15 @@ class CldMapCollision(C.Structure):
                 ("num_points_l", C.c_int32), ("num_points_w", C.c_int32), ("decay_rate", C.c_float), ("moving_speed_th", C.c_float)]
 
 
+class CldGoal(C.Structure):
+    """include/cld.h `cld_goal` (upstream's GlobalTargetPosLoss / GlobalTargetPosAtTimeLoss per agent, device pointers)."""
+    _fields_ = [("target_pos", C.c_void_p), ("agent_from_world", C.c_void_p), ("kind", C.c_void_p), ("target_time", C.c_void_p),
+                ("urgency", C.c_void_p), ("pref_speed", C.c_void_p), ("scale", C.c_void_p), ("reached", C.c_void_p),
+                ("num_samp", C.c_int32), ("global_t", C.c_int32), ("dt", C.c_float), ("min_progress_dist", C.c_float)]
+
+
+GOAL_KINDS = {"global_target_pos": 1, "global_target_pos_at_time": 2}      # cld_goal.kind (0 = off)
+
 _P = C.c_void_p
 # name -> (restype, argtypes); every symbol include/cld.h declares
 SIGNATURES = {
@@ -122,6 +131,8 @@ SIGNATURES = {
                                      C.c_int32, _P]),
     "cld_agent_collision": (C.c_int, [_P, _P, C.POINTER(CldCollision), _P, _P, _P, C.c_int32, _P]),
     "cld_map_collision_loss": (C.c_int, [_P, _P, C.POINTER(CldMapCollision), _P, _P, _P, C.c_int32, _P]),
+    "cld_goal_loss": (C.c_int, [_P, _P, C.POINTER(CldGoal), _P, _P, _P, C.c_int32, _P]),
+    "cld_set_goal_term": (C.c_int, [_P, C.POINTER(CldGoal)]),
     "cld_world_step": (C.c_int, [_P, _P, _P, _P, C.c_int32, _P, _P, C.c_int32, _P]),
     "cld_profile_enable": (C.c_int, [_P, C.c_int32]),
     "cld_profile_read": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double)]),

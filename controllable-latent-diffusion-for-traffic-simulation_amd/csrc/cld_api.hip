@@ -51,6 +51,8 @@ struct cld_handle_s {
     std::map<std::string, std::vector<float>> w;     // host copies keyed by reference state_dict name
     std::map<std::string, size_t> expect;            // name -> numel
     bool finalized = false, has_decoder = false, has_unet = false;
+    cld_goal goal{};                                 // cld_set_goal_term: the goal term every guided call adds while has_goal
+    bool has_goal = false;
     std::vector<void*> dev_allocs;
     // schedule (host, fp32 as in dm_model.py:29-56)
     std::vector<float> x_t_cof, noise_cof, plvc, sqrt_acp, sqrt_1m_acp, sqrt_recip_acp, sqrt_recipm1_acp;
@@ -1424,9 +1426,24 @@ static MapCollisionArgs map_args(const cld_map_collision* c, const float* traj, 
     return a;
 }
 
+static int check_goal(cld_handle h, const char* fn, const cld_goal* g, int B) {
+    if (!g->target_pos || !g->agent_from_world || !g->kind || !g->target_time || !g->urgency || !g->pref_speed || !g->scale)
+        return fail(h, CLD_ERR_ARG, std::string(fn) + ": goal term: null pointer");
+    if (g->num_samp < 1 || B % g->num_samp) return fail(h, CLD_ERR_ARG, std::string(fn) + ": goal term: B must be agents x num_samp");
+    return CLD_OK;
+}
+static GoalArgs goal_args(const cld_goal* g, const float* traj, const float* grad_in, float* loss, float* grad, int B) {
+    GoalArgs a{};
+    a.traj = traj; a.target_pos = g->target_pos; a.agent_from_world = g->agent_from_world; a.kind = g->kind; a.target_time = g->target_time;
+    a.urgency = g->urgency; a.pref_speed = g->pref_speed; a.scale = g->scale; a.reached = g->reached; a.grad_in = grad_in;
+    a.loss = loss; a.grad = grad; a.rows = B; a.num_samp = g->num_samp; a.global_t = g->global_t; a.dt = g->dt;
+    a.min_progress_dist = g->min_progress_dist;
+    return a;
+}
+
 static int check_guidance(cld_handle h, const char* fn, const cld_guidance* gd, int B) {
     if (!h->has_decoder) return fail(h, CLD_ERR_STATE, std::string(fn) + ": guidance needs the decoder weights");
-    if (!gd->curr_states || (!gd->target_speed && !gd->speed_limit_scale && !gd->acc_limit_scale && !gd->target_pos_scale && !gd->ext_grad && !gd->collision && !gd->map_collision))
+    if (!gd->curr_states || (!gd->target_speed && !gd->speed_limit_scale && !gd->acc_limit_scale && !gd->target_pos_scale && !gd->ext_grad && !gd->collision && !gd->map_collision && !h->has_goal))
         return fail(h, CLD_ERR_ARG, std::string(fn) + ": guidance needs curr_states and at least one loss term");
     if (gd->collision) {
         const int rcc = check_collision(h, fn, gd->collision, B);
@@ -1434,6 +1451,10 @@ static int check_guidance(cld_handle h, const char* fn, const cld_guidance* gd, 
     }
     if (gd->map_collision) {
         const int rcc = check_map_collision(h, fn, gd->map_collision, B);
+        if (rcc) return rcc;
+    }
+    if (h->has_goal) {
+        const int rcc = check_goal(h, fn, &h->goal, B);
         if (rcc) return rcc;
     }
     if (gd->grad_steps < 0 || gd->final_grad_steps < 0 || gd->grad_steps > 64 || gd->final_grad_steps > 64)
@@ -1470,7 +1491,7 @@ static int run_guidance(cld_handle h, const Ws& w, const cld_guidance* gd, int B
         const bool last = k == steps;
         g.opt_step = k;
         g.mean = k == 1 ? mean0 : w.gcur;
-        if (gd->collision || gd->map_collision) {    // the scene / map terms are functions of the decoded plans of the current iterate
+        if (gd->collision || gd->map_collision || h->has_goal) {    // the scene / map / goal terms are functions of the decoded plans of the current iterate
             if (B >= 256 && guide_forward_available(B, h->force_kernel[CLD_KERNEL_GUIDE]) && h->force_kernel[CLD_KERNEL_DECODE] == FORM_AUTO) {
                 // (from the batch size at which cld_decode itself would take its 16-agent MFMA form, ~0.3 ms; below that the
                 //  one-agent-per-workgroup decoder is the shorter chain: 64 agents 579 vs 616 us per collision-guided step)
@@ -1499,6 +1520,10 @@ static int run_guidance(cld_handle h, const Ws& w, const cld_guidance* gd, int B
         }
         if (gd->map_collision) {                     // adds to whatever gradient is there already (caller's ext_grad, agent collisions)
             HIPCK(h, launch_map_collision(map_args(gd->map_collision, w.col_traj, gd->collision ? w.col_grad : gd->ext_grad, nullptr, w.col_grad), B, s));
+            g.ext_grad = w.col_grad;
+        }
+        if (h->has_goal) {                           // likewise: on top of the caller's ext_grad and the collision gradients
+            HIPCK(h, launch_goal(goal_args(&h->goal, w.col_traj, (gd->collision || gd->map_collision) ? w.col_grad : gd->ext_grad, nullptr, w.col_grad, B), s));
             g.ext_grad = w.col_grad;
         }
         g.z = last ? z : nullptr;
@@ -1922,6 +1947,23 @@ int cld_map_collision_loss(cld_handle h, const float* traj, const cld_map_collis
     int rc = check_map_collision(h, "cld_map_collision_loss", c, B);
     if (rc) return rc;
     HIPCK(h, launch_map_collision(map_args(c, traj, grad_in, loss, grad), B, static_cast<hipStream_t>(stream)));
+    return CLD_OK;
+}
+
+int cld_goal_loss(cld_handle h, const float* traj, const cld_goal* g, const float* grad_in, float* loss, float* grad, int32_t B,
+                  void* stream) {
+    if (!h) return CLD_ERR_ARG;
+    if (!traj || !g || B < 1 || (!loss && !grad)) return fail(h, CLD_ERR_ARG, "cld_goal_loss: bad argument");
+    int rc = check_goal(h, "cld_goal_loss", g, B);
+    if (rc) return rc;
+    HIPCK(h, launch_goal(goal_args(g, traj, grad_in, loss, grad, B), static_cast<hipStream_t>(stream)));
+    return CLD_OK;
+}
+
+int cld_set_goal_term(cld_handle h, const cld_goal* g) {
+    if (!h) return CLD_ERR_ARG;
+    h->has_goal = g != nullptr;
+    h->goal = g ? *g : cld_goal{};
     return CLD_OK;
 }
 

@@ -375,6 +375,26 @@ struct MapCollisionArgs {
 };
 hipError_t launch_map_collision(const MapCollisionArgs& a, int rows, hipStream_t s);
 
+// upstream's GlobalTargetPosLoss / GlobalTargetPosAtTimeLoss + their gradient w.r.t. the decoded plans (goal_kernels.hip;
+// guidance_loss.py:876-1135)
+struct GoalArgs {
+    const float* traj;               // [rows = A * num_samp, 52, 6] descaled plans, sample-minor
+    const float* target_pos;         // [A, 2] world frame
+    const float* agent_from_world;   // [A, 3, 3]
+    const int* kind;                 // [A] 0 = off, 1 = global_target_pos, 2 = global_target_pos_at_time
+    const int* target_time;          // [A] global step index (kind 2)
+    const float* urgency;            // [A]
+    const float* pref_speed;         // [A]
+    const float* scale;              // [A] d total / d value of the agent's rows
+    const unsigned char* reached;    // [A] or null: have_reached_mask
+    const float* grad_in;            // [rows, 52, 6] or null (may alias grad)
+    float* loss;                     // [rows] or null
+    float* grad;                     // [rows, 52, 6] or null
+    int rows, num_samp, global_t;
+    float dt, min_progress_dist;
+};
+hipError_t launch_goal(const GoalArgs& a, hipStream_t s);
+
 // PPO reward (models/rl/criticmodel.py:7-64)
 struct RewardArgs {
     const float* traj;                // [B,52,6] descaled (x, y, v, yaw, acc, yaw-rate), agent frame

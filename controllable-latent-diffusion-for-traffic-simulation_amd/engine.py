@@ -5,6 +5,7 @@ runs in the HIP library behind the C-ABI of include/cld.h.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 from typing import Mapping, Optional
 
@@ -304,7 +305,8 @@ class Engine:
     def _guidance(self, g: Mapping, B: int):
         """dict(curr_states [B,4], target_speed [B,52] | None, loss_scale [B] | None, speed_limit (limit, scale) | None,
         acc_limit (limit, scale) | None, target_pos (pos [B,2], time index [B], scale) | None, lr | None, perturb_th | None | "sigma", optimizer "adam" | "sgd",
-        grad_steps = 1, guide_clean = False, agent_collision: dict | None (see _collision), map_collision: dict | None (see _map_collision))
+        grad_steps = 1, guide_clean = False, agent_collision: dict | None (see _collision), map_collision: dict | None (see _map_collision),
+        goal: dict | None (see _goal; not part of the struct: sample / sample_step / guidance_step keep it on the handle for the call))
         -> (CldGuidance, tensors kept alive).  A `scale` is a per-agent tensor [B] (weight / (agents of the scene * 52),
         as DiffuserGuidance averages) or a scalar weight (divided by 52 here).  lr None = sigma_t; perturb_th None = no clip (what
         the reference's perturb() does), "sigma" = clip to sigma_t, a number = clip to it (include/cld.h)."""
@@ -447,6 +449,69 @@ class Engine:
                                   float(c.get("guide_moving_speed_th", 0.5)))
         return cc, (ext, rfa, dm, spd, start, wts)
 
+    def _goal(self, c: Mapping, B: int):
+        """dict(kind [A] (0 off | 1 global_target_pos | 2 global_target_pos_at_time, _lib.GOAL_KINDS), target_pos [A,2] (world),
+        target_time [A] (rollout steps; kind 2), urgency [A], pref_speed [A], scale [A] (weight / agents of the config),
+        agent_from_world [A,3,3], reached [A] | None, global_t = 0, dt = 0.1, min_progress_dist = 0.5, num_samp = 1)
+        -> (CldGoal, tensors kept alive): upstream's GlobalTargetPosLoss / GlobalTargetPosAtTimeLoss
+        (src/tbsim/utils/guidance_loss.py:876-1135) per agent.  B = A * num_samp."""
+        N = int(c.get("num_samp", 1))
+        if N < 1 or B % N:
+            raise CldError(f"goal: {B} rows are not a multiple of num_samp = {N}")
+        A = B // N
+        missing = [k for k in ("kind", "target_pos", "urgency", "pref_speed", "scale", "agent_from_world") if c.get(k) is None]
+        if missing:
+            raise CldError(f"goal: missing {missing}")
+
+        def i32(v, what):
+            t = torch.as_tensor(v).to(self.device, torch.int32).contiguous()
+            if tuple(t.shape) != (A,):
+                raise CldError(f"goal {what}: expected shape ({A},), got {tuple(t.shape)}")
+            return t
+        kind = i32(c["kind"], "kind")
+        tt = i32(c["target_time"], "target_time") if c.get("target_time") is not None else torch.zeros(A, dtype=torch.int32, device=self.device)
+        tp = self._f32(c["target_pos"], (A, 2)); afw = self._f32(c["agent_from_world"], (A, 3, 3))
+        urg = self._f32(c["urgency"], (A,)); ps = self._f32(c["pref_speed"], (A,)); sc = self._f32(c["scale"], (A,))
+        rd = None
+        if c.get("reached") is not None:
+            rd = (torch.as_tensor(c["reached"]) != 0).to(self.device, torch.uint8).contiguous()
+            if tuple(rd.shape) != (A,):
+                raise CldError(f"goal reached: expected shape ({A},), got {tuple(rd.shape)}")
+        cg = _lib.CldGoal(tp.data_ptr(), afw.data_ptr(), kind.data_ptr(), tt.data_ptr(), urg.data_ptr(), ps.data_ptr(), sc.data_ptr(),
+                          None if rd is None else rd.data_ptr(), N, int(c.get("global_t", 0)), float(c.get("dt", 0.1)),
+                          float(c.get("min_progress_dist", 0.5)))
+        return cg, (tp, afw, kind, tt, urg, ps, sc, rd)
+
+    @contextlib.contextmanager
+    def _goal_term(self, guidance: Optional[Mapping], B: int):
+        """The `goal` entry of a guidance dict kept on the handle for the library call inside (cld_set_goal_term), and cleared
+        behind it whatever happens: no term outlives the call that set it."""
+        g = None if guidance is None else guidance.get("goal")
+        if g is None:
+            yield
+            return
+        cg, keep = self._goal(g, B)
+        self._check(self.lib.cld_set_goal_term(self._h, C.byref(cg)), "cld_set_goal_term")
+        try:
+            yield
+        finally:
+            self.lib.cld_set_goal_term(self._h, None)
+
+    def goal_loss(self, traj, goal: Mapping, grad_in=None, want_grad=True):
+        """Upstream's global waypoint losses on decoded plans [B,52,6] (descaled, sample-minor rows; `goal`: see _goal) ->
+        (per-row values [B] as upstream files them under guide_losses, grad_in + scale * d value / d traj [B,52,6]); cld_goal_loss."""
+        traj = self._f32(traj)
+        B = traj.shape[0]
+        traj = self._f32(traj, (B, T, 6))
+        cg, keep = self._goal(goal, B)
+        gi = None if grad_in is None else self._f32(grad_in, (B, T, 6))
+        loss = torch.empty(B, dtype=torch.float32, device=self.device)
+        grad = torch.empty(B, T, 6, dtype=torch.float32, device=self.device) if want_grad else None
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cld_goal_loss(self._h, _ptr(traj), C.byref(cg), _ptr(gi), _ptr(loss), _ptr(grad), B, self._stream()),
+                        "cld_goal_loss")
+        return (loss, grad) if want_grad else loss
+
     def map_collision(self, traj, cfg: Mapping, grad_in=None, want_grad=True):
         """Upstream's MapCollisionLoss on decoded plans [B,52,6] (descaled, sample-minor rows) -> (per-plan values [B],
         d total / d traj [B,52,6]); cld_map_collision_loss."""
@@ -504,7 +569,7 @@ class Engine:
         xn = torch.empty_like(mean) if z is not None else None
         gr = torch.empty_like(mean) if want_grad else None
         ws, wsn = self._workspace(B)
-        with torch.cuda.device(self.device):
+        with torch.cuda.device(self.device), self._goal_term(guidance, B):
             self._check(self.lib.cld_guidance_step(self._h, _ptr(mean), _ptr(cond), C.byref(cg), C.c_float(sigma), _ptr(z),
                                                    _ptr(mg), _ptr(xn), _ptr(gr), B, ws, wsn, self._stream()), "cld_guidance_step")
         out = (mg,) + ((xn,) if z is not None else ()) + ((gr,) if want_grad else ())
@@ -565,7 +630,7 @@ class Engine:
         x1 = torch.empty_like(x_T) if (want_x1 and 1 in range(0, self.n_timesteps, self.stride)) else None
         logp = torch.empty(B, dtype=torch.float32, device=self.device) if want_logp else None
         cfg = non_cond is not None and guidance_w != 0.0
-        with torch.cuda.device(self.device):
+        with torch.cuda.device(self.device), self._goal_term(guidance, B):
             if guidance is not None:
                 cg, keep = self._guidance(guidance, B)
                 non_cond = self._f32(non_cond, (B, COND)) if cfg else None
@@ -604,7 +669,7 @@ class Engine:
         gr = torch.empty_like(x_t) if guided and want_grad else None
         ws, wsn = self._workspace(2 * ((B + 15) // 16 * 16) if cfg else B)
         sigma = C.c_float()
-        with torch.cuda.device(self.device):
+        with torch.cuda.device(self.device), self._goal_term(guidance, B):
             self._check(self.lib.cld_sample_step(self._h, _ptr(x_t), _ptr(cond), _ptr(non_cond), C.c_float(guidance_w),
                                                  None if cg is None else C.byref(cg), int(t_idx), _ptr(z), _ptr(xn), _ptr(mean),
                                                  _ptr(mg), _ptr(gr), C.byref(sigma), B, ws, wsn, self._stream()), "cld_sample_step")

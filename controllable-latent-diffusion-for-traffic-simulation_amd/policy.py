@@ -50,6 +50,7 @@ class Action:
 
 
 SCENE_LEVEL_LOSSES = ("agent_collision", "social_group", "gptcollision", "gptkeepdistance")
+GOAL_KINDS = {"global_target_pos": 1, "global_target_pos_at_time": 2}       # cld_goal.kind (include/cld.h); per-agent selection: not scene-level
 LOSS_COLUMN = {"target_speed": 0, "speed_limit": 1, "acc_limit": 2, "target_pos_at_time": 3, "target_pos": 3}   # cld_guidance_losses
 
 
@@ -97,6 +98,57 @@ def choose_action_from_gt(positions, target_positions, target_availabilities):
     return act_idx
 
 
+def invert_frames(m):
+    """Inverse of 2-D affine frames [...,3,3] (last row 0 0 1) in closed form: world_from_agent <-> agent_from_world."""
+    a, b, tx, c, d, ty = m[..., 0, 0], m[..., 0, 1], m[..., 0, 2], m[..., 1, 0], m[..., 1, 1], m[..., 1, 2]
+    det = a * d - b * c
+    ia, ib, ic, id_ = d / det, -b / det, -c / det, a / det
+    out = torch.zeros_like(m)
+    out[..., 0, 0], out[..., 0, 1], out[..., 0, 2] = ia, ib, -(ia * tx + ib * ty)
+    out[..., 1, 0], out[..., 1, 1], out[..., 1, 2] = ic, id_, -(ic * tx + id_ * ty)
+    out[..., 2, 2] = 1.0
+    return out
+
+
+def frames_from_pose(world):
+    """world [B,3] = (x, y, heading) -> world_from_agent [B,3,3]."""
+    c, s = torch.cos(world[:, 2]), torch.sin(world[:, 2])
+    W = torch.zeros(world.shape[0], 3, 3, dtype=world.dtype, device=world.device)
+    W[:, 0, 0], W[:, 0, 1], W[:, 0, 2] = c, -s, world[:, 0]
+    W[:, 1, 0], W[:, 1, 1], W[:, 1, 2] = s, c, world[:, 1]
+    W[:, 2, 2] = 1.0
+    return W
+
+
+def transform_points(pts, m):
+    """pts [B,K,2] through the frames m [B,3,3] (GeoUtils.transform_points_tensor)."""
+    return pts @ m[:, :2, :2].transpose(1, 2) + m[:, None, :2, 2]
+
+
+def update_goal_reached(reached, goal: Mapping, world_from_agent, agent_hist, by: str = "any"):
+    """have_reached_mask of the goal losses after one more observation (guidance_loss.py:1019-1029, :1122-1133) -> new mask [B]
+    (a set flag stays set).  Per config with a tolerance: the last `action_num` history positions go to the world frame and an agent
+    is flagged when one lies within the tolerance of its target.  by="any" reproduces the reference as written: only the FIRST of
+    those points is kept after the transform, and its [M,2] - [M,1,2] broadcast takes the minimum over the points of ALL the config's
+    agents, so agent i is flagged when any of them is near i's target.  by="own": the agent's own `action_num` points."""
+    if by not in ("any", "own"):
+        raise ValueError(f"goal_reached_by={by!r} (any | own)")
+    reached = reached.clone()
+    world_from_agent = world_from_agent.to(agent_hist.device)
+    for idx, tol, action_num in goal["configs"]:
+        if tol is None:
+            continue
+        idx_d = idx.to(agent_hist.device)
+        hw = transform_points(agent_hist[idx_d][:, -int(action_num):, :2].float(), world_from_agent[idx_d].float())      # [M,K,2]
+        tgt = goal["target_pos"][idx].to(hw.device, hw.dtype)
+        if by == "any":
+            dist = (hw[:, 0][None, :, :] - tgt[:, None, :]).norm(dim=-1).min(dim=-1)[0]
+        else:
+            dist = (hw - tgt[:, None, :]).norm(dim=-1).min(dim=-1)[0]
+        reached[idx] |= (dist < float(tol)).cpu()
+    return reached
+
+
 class CldPolicy:
     def __init__(self, dm: DmModel, vae: VaeModel, context_encoder: Optional[Callable] = None,
                  disable_control_on_stationary: bool = False, moving_speed_th: float = 0.5, select_per_scene: bool = False):
@@ -107,6 +159,11 @@ class CldPolicy:
         self.select_per_scene = select_per_scene      # False = upstream's sample selection as written (see choose_action_from_guidance)
         self._guidance = None
         self._guidance_cfg = None                     # (guidance_config_list, scene_index) behind self._guidance
+        # closed-loop state of the goal losses (upstream keeps it on the loss objects): have_reached_mask [B], the rollout step of the
+        # last get_action, and how the mask is updated ("any": the reference as written | "own", see update_goal_reached)
+        self.goal_reached = None
+        self.goal_global_t = None
+        self.goal_reached_by = "any"
 
     def eval(self):
         return self
@@ -116,12 +173,43 @@ class CldPolicy:
         `get_action` calls.  `opt`: lr / optimizer / perturb_th of the optimiser step (scene_edit_config.py:74-90), `output`
         (True | dict: guidance on the t = 0 output, upstream apply_guidance_output + final_step_opt_params), `intermediate`."""
         data_batch = opt.pop("data_batch", None)         # observation fields scene-coupled losses read (agent_collision: extent, world_from_agent, curr_speed)
+        by = opt.pop("goal_reached_by", "any")
+        if by not in ("any", "own"):
+            raise ValueError(f"goal_reached_by={by!r} (any | own)")
         self._guidance = dict(guidance_from_config(guidance_config_list, scene_index, data_batch=data_batch), **opt)
         self._guidance_cfg = (guidance_config_list, torch.as_tensor(scene_index).reshape(-1).cpu())
+        # a new configuration starts with nobody arrived (upstream builds new loss objects: have_reached_mask = None)
+        self.goal_reached_by = by
+        self.goal_global_t = None
+        self.goal_reached = torch.zeros(self._guidance_cfg[1].numel(), dtype=torch.bool) if self._guidance.get("goal") is not None else None
 
     def clear_guidance(self):
         self._guidance = None
         self._guidance_cfg = None
+        self.goal_reached = None
+        self.goal_global_t = None
+
+    def _goal_for_step(self, goal: Mapping, obs_dict: Mapping, step_index: int, carry: bool):
+        """The `goal` entry of a guidance dict completed for one get_action: global_t = step_index (upstream
+        update_guidance(global_t=kwargs['step_index']), algos.py:2048), the frames of this observation, and -- `carry`: the goal was
+        configured by set_guidance -- the reached mask, updated from obs_dict['agent_hist'] before sampling and kept for the next call."""
+        W, M = obs_dict.get("world_from_agent"), obs_dict.get("agent_from_world")
+        if goal.get("agent_from_world") is not None and not carry:
+            M = goal["agent_from_world"]
+        if W is None and M is None:
+            raise ValueError("a goal loss needs obs_dict['agent_from_world'] or obs_dict['world_from_agent']")
+        W = None if W is None else torch.as_tensor(W).float()
+        M = invert_frames(W) if M is None else torch.as_tensor(M).float()
+        out = dict(goal, agent_from_world=M, global_t=int(step_index))
+        if carry:
+            if any(tol is not None for _, tol, _ in goal["configs"]):
+                if obs_dict.get("agent_hist") is None:
+                    raise ValueError("a goal loss with a target_tolerance needs obs_dict['agent_hist']")
+                self.goal_reached = update_goal_reached(self.goal_reached, goal, invert_frames(M) if W is None else W,
+                                                        torch.as_tensor(obs_dict["agent_hist"]), self.goal_reached_by)
+            self.goal_global_t = int(step_index)
+            out["reached"] = self.goal_reached.clone()
+        return out
 
     def _guide_losses(self, traj, g, B: int, N: int, from_cfg: bool):
         """-> (guide_losses dict name -> [B,N] as upstream keys them, per-scene loss names) from the library's per-agent values;
@@ -130,7 +218,9 @@ class CldPolicy:
         vals = (self.vae.engine.guidance_losses(traj.reshape(B * N, 52, 6), g).reshape(B, N, 4) if has_builtin
                 else torch.full((B, N, 4), float("nan"), device=traj.device))
         nan = torch.full((B, N), float("nan"), device=vals.device)
-        colv = mapv = None
+        colv = mapv = goalv = None
+        if g.get("goal") is not None:                # unweighted per-row values, 0 for agents that have arrived (guidance_loss.py:1029,1133)
+            goalv = self.vae.engine.goal_loss(traj.reshape(B * N, 52, 6), dict(g["goal"], num_samp=N), want_grad=False).reshape(B, N)
         if g.get("agent_collision") is not None:     # per-agent values as upstream files them (unweighted; :2166-2168)
             colv = self.vae.engine.agent_collision(traj.reshape(B * N, 52, 6), dict(g["agent_collision"], num_samp=N), want_grad=False).reshape(B, N)
         if g.get("map_collision") is not None:
@@ -147,7 +237,8 @@ class CldPolicy:
                     mask = torch.zeros(B, dtype=torch.bool)
                     mask[idx] = True
                     mask = mask.to(vals.device)
-                    v = colv if c["name"] == "agent_collision" else (mapv if c["name"] == "map_collision" else vals[..., LOSS_COLUMN[c["name"]]])
+                    v = (colv if c["name"] == "agent_collision" else mapv if c["name"] == "map_collision" else
+                         goalv if c["name"] in GOAL_KINDS else vals[..., LOSS_COLUMN[c["name"]]])
                     out["%s_scene_%03d_%02d" % (c["name"], si, gi)] = torch.where(mask[:, None], v, nan)
         else:       # a plain `guidance=` dict: one scene, one entry per active term
             names.append([])
@@ -161,6 +252,12 @@ class CldPolicy:
             if mapv is not None:
                 out["map_collision_scene_000_%02d" % len(names[0])] = mapv
                 names[0].append("map_collision")
+            if goalv is not None:
+                kind = torch.as_tensor(g["goal"]["kind"]).to(goalv.device)
+                for nm, k in GOAL_KINDS.items():
+                    if bool((kind == k).any()):
+                        out["%s_scene_000_%02d" % (nm, len(names[0]))] = torch.where((kind == k)[:, None], goalv, nan)
+                        names[0].append(nm)
         return out, names
 
     @torch.no_grad()
@@ -174,7 +271,11 @@ class CldPolicy:
         obs_dict['target_positions'] (algos.py:2055-2056); `guide_clean=True`: the guidance steps act on the model's clean
         prediction (diffuser.py:866-873; its "video_diff" variant, which re-derives the posterior, is not built and raises).  A
         collision config (`agent_collision`, guidance_loss.py:442-630) is filed under guide_losses and makes the sample choice
-        scene-level, as upstream's SCENE_LEVEL_LOSSES do.  Not built: `plan` -- it raises instead of being ignored."""
+        scene-level, as upstream's SCENE_LEVEL_LOSSES do.  A goal config (`global_target_pos`, `global_target_pos_at_time`,
+        guidance_loss.py:930-1135) reads obs_dict['agent_from_world'] and / or ['world_from_agent'] [B,3,3] (one is computed from the
+        other; ValueError without both) and, with a target_tolerance, obs_dict['agent_hist'] [B,Th,>=2]; `step_index` is its global_t
+        (algos.py:2048); the arrival flags persist on the policy (`goal_reached`) and come back as info['goal_reached'].
+        Not built: `plan` -- it raises instead of being ignored."""
         if guide_clean not in (False, True, 0, 1, None):
             raise NotImplementedError(f"guide_clean={guide_clean!r}: only the boolean form is built (diffuser.py:866-873)")
         if plan is not None:
@@ -195,6 +296,10 @@ class CldPolicy:
         g = guidance if guidance is not None else self._guidance
         if g is not None and guide_clean:
             g = dict(g, guide_clean=True)
+        from_cfg = g is self._guidance and self._guidance_cfg is not None
+        if g is not None and g.get("goal") is not None:
+            carry = guidance is None
+            g = dict(g, goal=self._goal_for_step(g["goal"], obs_dict, step_index, carry))
         out = self.dm({"history_positions": cond}, {k: aux[k] for k in ("cond_feat", "curr_states", "non_cond_feat") if k in aux},
                       {"num_samp": N}, noise=noise, class_free_guide_w=class_free_guide_w,
                       guidance=None if guide_as_filter_only else g)
@@ -206,7 +311,6 @@ class CldPolicy:
         if guide_with_gt and "target_positions" in obs_dict:
             act_idx = choose_action_from_gt(pos, obs_dict["target_positions"], obs_dict["target_availabilities"])
         elif g is not None:
-            from_cfg = g is self._guidance and self._guidance_cfg is not None
             g_rep = repeat_guidance({k: v for k, v in g.items() if k != "curr_states"}, N, a["curr_states"])
             losses, names = self._guide_losses(traj, g_rep, B, N, from_cfg)
             scene_of_agent = None
@@ -222,6 +326,10 @@ class CldPolicy:
             pos[still] = 0
             yaw[still] = 0
             executed[still] = executed[still] * torch.tensor([0.0, 0.0, 1.0, 0.0, 1.0, 1.0], device=pos.device)   # x, y, yaw of the executed plan
+        if g is not None and g.get("goal") is not None:
+            info["goal_global_t"] = g["goal"]["global_t"]
+            if g["goal"].get("reached") is not None:
+                info["goal_reached"] = torch.as_tensor(g["goal"]["reached"]).clone()
         info.update(action_samples=Action(pos, yaw).to_dict(), trajectories=traj, act_idx=act_idx, executed_trajectory=executed)
         return Action(pos[ar, act_idx], yaw[ar, act_idx]), info
 
@@ -238,6 +346,11 @@ def closed_loop_rollout(policy: CldPolicy, cond_fn: Callable, centroid, yaw, cur
     `parallel.gather_trajectories`) runs once per sim step; `timers` (`cld_amd.timer.Timers`) collects the per-phase
     times under the reference's keys "obs" / "network" / "env_step" / "step" (env_utils.py:268-298).
     The world moves on the EXECUTED trajectory (the selected sample, stationary agents held in place).
+    With a goal loss configured (`global_target_pos`, `global_target_pos_at_time`) the observation must tell get_action where the
+    agents are and where they have been; the fields `cond_fn`'s observation lacks are filled in here: `world_from_agent` /
+    `agent_from_world` [B,3,3] from the current world pose, and `agent_hist` [B,n_step_action,2]: the `n_step_action` executed states
+    of the previous plan taken into the new agent frame (the last one is the agent's position now), on the first step the current
+    position repeated.  `step_index` = the sim step is the goal losses' global_t.
     Returns the world poses after each sim step [n_sim_steps, B, 3]."""
     import inspect
     from contextlib import nullcontext
@@ -250,17 +363,34 @@ def closed_loop_rollout(policy: CldPolicy, cond_fn: Callable, centroid, yaw, cur
     except (TypeError, ValueError):
         four = False
     poses, plans = [], None
+    hist_world = None                                 # executed states of the previous plan, world frame [B,n_step_action,2]
     for step in range(n_sim_steps):
         with tm("step"):
             with tm("obs"):
                 o = cond_fn(step, world, cs, plans) if four else cond_fn(step, world, cs)
                 obs = o if isinstance(o, Mapping) else {"cond_feat": o, "curr_states": cs}
+                gk = get_action_kwargs.get("guidance")
+                has_goal = (gk if gk is not None else (policy._guidance or {})).get("goal") is not None
+                if has_goal:
+                    obs = dict(obs)
+                    W = frames_from_pose(world)
+                    if "world_from_agent" not in obs and "agent_from_world" not in obs:
+                        obs["world_from_agent"] = W
+                    if "agent_from_world" not in obs:
+                        obs["agent_from_world"] = invert_frames(obs["world_from_agent"])
+                    if "world_from_agent" not in obs:
+                        obs["world_from_agent"] = invert_frames(obs["agent_from_world"])
+                    if "agent_hist" not in obs:
+                        hw = world[:, None, :2].expand(-1, n_step_action, -1) if hist_world is None else hist_world
+                        obs["agent_hist"] = transform_points(hw, torch.as_tensor(obs["agent_from_world"]).float().to(hw.device))
             with tm("network"):
                 _, info = policy.get_action(obs, step_index=step, **get_action_kwargs)
                 traj = info["executed_trajectory"].contiguous()
             with tm("env_step"):
                 if gather is not None:
                     plans = gather(traj)
+                if has_goal:
+                    hist_world = transform_points(traj[:, :n_step_action, :2], frames_from_pose(world))
                 world, cs = eng.world_step(traj, world[:, :2].contiguous(), world[:, 2].contiguous(), n_step_action - 1)
         poses.append(world)
     return torch.stack(poses)
@@ -276,8 +406,11 @@ def guidance_from_config(guidance_config_list, scene_index, horizon: int = 52, d
     per-agent scales of the kernel: weight / (agents * horizon) for the per-step losses, weight / agents for the waypoint
     losses.  Supported names: target_speed, speed_limit, acc_limit, target_pos_at_time, target_pos, agent_collision (needs
     `data_batch` with `extent`, `world_from_agent`, `curr_speed`: the observation fields upstream's loss reads,
-    guidance_loss.py:506-510) and map_collision (`extent`, `raster_from_agent`, `drivable_map`, `curr_speed`, :773-775); at most
-    one of each per scene, one parameter set per call; the others (social groups, stop signs, lane keeping, ...) are not built.  One speed / acceleration limit value per call."""
+    guidance_loss.py:506-510), map_collision (`extent`, `raster_from_agent`, `drivable_map`, `curr_speed`, :773-775) and the world-frame
+    waypoint losses global_target_pos / global_target_pos_at_time (:930-1135; params target_pos, target_time, urgency, pref_speed = 1.42,
+    dt = 0.1, min_progress_dist = 0.5, target_tolerance = None / 2, action_num = 5, all indexed by the config's `agents`; scale =
+    weight / agents; at most one per agent, one dt and one min_progress_dist per call); at most
+    one of each other loss per scene, one parameter set per call; the others (social groups, stop signs, lane keeping, ...) are not built.  One speed / acceleration limit value per call."""
     scene_index = torch.as_tensor(scene_index).reshape(-1).cpu()
     B = scene_index.numel()
     _, local = torch.unique_consecutive(scene_index, return_inverse=True)
@@ -287,7 +420,7 @@ def guidance_from_config(guidance_config_list, scene_index, horizon: int = 52, d
     ts_scale = torch.zeros(B); ts = torch.zeros(B, horizon); has_ts = False
     sl_scale = torch.zeros(B); al_scale = torch.zeros(B); sl = al = None
     tp = torch.zeros(B, 2); tt = torch.zeros(B, dtype=torch.int32); tp_scale = torch.zeros(B); has_tp = False
-    col = mcol = None
+    col = mcol = goal = None
     for si, cfgs in enumerate(guidance_config_list):
         members = torch.nonzero(local == si).reshape(-1)
         for cfg in cfgs:
@@ -358,9 +491,52 @@ def guidance_from_config(guidance_config_list, scene_index, horizon: int = 52, d
                 if mcol["weight"][si] != 0.0:
                     raise ValueError("two map_collision losses on one scene")
                 mcol["weight"][si] = wgt
+            elif name in GOAL_KINDS:
+                # GlobalTargetPosLoss / GlobalTargetPosAtTimeLoss (guidance_loss.py:930-1135): the parameters are indexed by the config's
+                # `agents` (upstream asserts x.size(0) == target_pos.size(0) AFTER masking); frames, global_t and the reached mask
+                # come with every get_action (CldPolicy._goal_for_step)
+                M = idx.numel()
+                if goal is None:
+                    goal = dict(kind=torch.zeros(B, dtype=torch.int32), target_pos=torch.zeros(B, 2), target_time=torch.zeros(B, dtype=torch.int32),
+                                urgency=torch.zeros(B), pref_speed=torch.full((B,), 1.42), scale=torch.zeros(B), dt=None, min_progress_dist=None,
+                                configs=[])
+                if bool((goal["kind"][idx] != 0).any()):
+                    raise ValueError("two goal losses on one agent")
+
+                def per_agent(key, default=None, dtype=torch.float32):
+                    v = prm.get(key, default)
+                    if v is None:
+                        raise ValueError(f"{name} needs params['{key}']")
+                    v = torch.as_tensor(v, dtype=dtype).reshape(-1)
+                    if v.numel() not in (1, M):
+                        raise ValueError(f"{name}: params['{key}'] must hold one entry per agent of the config ({M}), got {v.numel()}")
+                    return v.expand(M)
+                tpos = torch.as_tensor(prm["target_pos"], dtype=torch.float32).reshape(-1, 2)
+                if tpos.shape[0] != M:
+                    raise ValueError(f"{name}: params['target_pos'] must hold one position per agent of the config ({M}), got {tpos.shape[0]}")
+                goal["kind"][idx] = GOAL_KINDS[name]
+                goal["target_pos"][idx] = tpos
+                goal["urgency"][idx] = per_agent("urgency")
+                goal["pref_speed"][idx] = per_agent("pref_speed", 1.42)
+                goal["scale"][idx] = wgt / n
+                dt = float(prm.get("dt", 0.1))
+                if goal["dt"] is not None and goal["dt"] != dt:
+                    raise ValueError("one dt per call for the goal losses")
+                goal["dt"] = dt
+                if name == "global_target_pos":
+                    mpd = float(prm.get("min_progress_dist", 0.5))
+                    if goal["min_progress_dist"] is not None and goal["min_progress_dist"] != mpd:
+                        raise ValueError("one min_progress_dist per call")
+                    goal["min_progress_dist"] = mpd
+                    tol = prm.get("target_tolerance", None)
+                else:
+                    goal["target_time"][idx] = per_agent("target_time", dtype=torch.int32)
+                    tol = prm.get("target_tolerance", 2)
+                goal["configs"].append((idx.clone(), None if tol is None else float(tol), int(prm.get("action_num", 5))))
             else:
                 raise NotImplementedError(f"guidance loss '{name}' is not built (target_speed, speed_limit, acc_limit, "
-                                          f"target_pos_at_time, target_pos, agent_collision, map_collision are)")
+                                          f"target_pos_at_time, target_pos, agent_collision, map_collision, global_target_pos, "
+                                          f"global_target_pos_at_time are)")
     if has_ts:
         out["target_speed"], out["loss_scale"] = ts, ts_scale
     if sl is not None:
@@ -374,6 +550,10 @@ def guidance_from_config(guidance_config_list, scene_index, horizon: int = 52, d
         out["agent_collision"] = col
     if mcol is not None:
         out["map_collision"] = mcol
+    if goal is not None:
+        if goal["min_progress_dist"] is None:
+            goal["min_progress_dist"] = 0.5
+        out["goal"] = goal
     if not out:
         raise ValueError("no guidance loss configured")
     return out

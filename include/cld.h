@@ -294,6 +294,44 @@ typedef struct cld_map_collision {
 int cld_map_collision_loss(cld_handle h, const float* traj, const cld_map_collision* c, const float* grad_in, float* loss,
                            float* grad, int32_t B, void* stream);
 
+/* Upstream's GlobalTargetPosLoss (`global_target_pos`) and GlobalTargetPosAtTimeLoss (`global_target_pos_at_time`),
+ * src/tbsim/utils/guidance_loss.py:876-1135: a waypoint in the WORLD frame, taken into the agent frame of the current plan
+ * (p = agent_from_world[a] target_pos[a]), H = 52, d_t = |pos_t - p|.  Per agent, by kind[a]:
+ *   0  off: value 0, no gradient
+ *   1  |p| <  H dt pref_speed: TargetPosLoss with min_target_time = 0, mean_t(softmin_t(d) d_t^2)
+ *      otherwise:              relu(max(urgency H dt pref_speed, min_progress_dist) - (d_0 - d_51))
+ *   2  lt = target_time[a] - global_t:  lt < 0: 0;  0 <= lt < H: d_lt (TargetPosAtTimeLoss);
+ *      lt >= H: relu(d_51 - lt dt pref_speed (1 - urgency))
+ * Agents with reached[a] != 0 (upstream's have_reached_mask; the caller keeps it across plans) have value 0 and no gradient.
+ * Agents A = B / num_samp; rows of traj are sample-minor as in cld_collision.  The arrays stay the caller's. */
+typedef struct cld_goal {
+    const float* target_pos;        /* DEVICE [A,2] world frame                                                           */
+    const float* agent_from_world;  /* DEVICE [A,3,3] row-major                                                           */
+    const int32_t* kind;            /* DEVICE [A] 0 / 1 / 2, see above                                                    */
+    const int32_t* target_time;     /* DEVICE [A] target time of kind 2 in rollout steps (the same clock as global_t)     */
+    const float* urgency;           /* DEVICE [A] in [0, 1]                                                               */
+    const float* pref_speed;        /* DEVICE [A] m/s (upstream default 1.42)                                             */
+    const float* scale;             /* DEVICE [A] d total / d value: weight / agents of the config                        */
+    const uint8_t* reached;         /* DEVICE [A] or NULL                                                                 */
+    int32_t num_samp;
+    int32_t global_t;               /* rollout step of this plan (upstream update_guidance(global_t=step_index))          */
+    float dt;                       /* 0.1                                                                                */
+    float min_progress_dist;        /* 0.5                                                                                */
+} cld_goal;
+
+/* The loss above on given plans: traj [B,52,6] descaled -> loss [B] = the unweighted per-row values, as upstream files them
+ * under `guide_losses`, and grad [B,52,6] = grad_in (when given; may be grad itself) + scale[agent] * d value / d traj: only the
+ * x, y columns of the steps the value reads get a contribution.  Either output may be NULL.  Deterministic: no atomics. */
+int cld_goal_loss(cld_handle h, const float* traj, const cld_goal* g, const float* grad_in, float* loss, float* grad,
+                  int32_t B, void* stream);
+
+/* Keep a goal term on the handle (the struct is copied by value; NULL clears it).  While one is set, every guided call
+ * (cld_sample_guided, cld_sample_step, cld_guidance_step) adds it to the guidance loss: each optimiser step decodes the current
+ * iterate as for the collision terms, and the gradient above joins the caller's ext_grad and the collision gradients as the
+ * guidance kernel's ext_grad.  A set term counts as a loss term of the `cld_guidance` it is used with.  (A setter and not a
+ * pointer in cld_guidance: that struct's layout is frozen.) */
+int cld_set_goal_term(cld_handle h, const cld_goal* g);
+
 /* cld_sample (non_cond == NULL) / cld_sample_cfg (non_cond != NULL) with the guidance step above inside the loop. */
 int cld_sample_guided(cld_handle h, const float* x_T, const float* noise, const float* cond, const float* non_cond,
                       float guidance_w, const cld_guidance* guidance, int32_t steps, float* x0, float* x1, float* logp,
