@@ -1380,7 +1380,7 @@ int cld_ddpm_step(cld_handle h, const float* x, const float* cond, int32_t t_idx
                   float* mean, float* sigma_host, int32_t B, void* workspace, size_t workspace_bytes, void* stream) {
     int rc = check_common(h, "cld_ddpm_step", B, t_idx, workspace, workspace_bytes);
     if (rc) return rc;
-    if (!x || !cond || (!z && x_next && t_idx != 0)) return fail(h, CLD_ERR_ARG, "cld_ddpm_step: null pointer");
+    if (!x || !cond) return fail(h, CLD_ERR_ARG, "cld_ddpm_step: null pointer");      // z NULL: the generator, seed 0 / step 0 (a{} below)
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int bp = pad16(B);
     Ws w = carve(workspace, bp);
@@ -1631,7 +1631,7 @@ int cld_sample_step(cld_handle h, const float* x_t, const float* cond, const flo
     const bool cfg = non_cond != nullptr;
     int rc = check_common(h, "cld_sample_step", cfg ? 2 * pad16(B) : B, t_idx, workspace, workspace_bytes);
     if (rc) return rc;
-    if (!x_t || !cond || (!z && t_idx != 0)) return fail(h, CLD_ERR_ARG, "cld_sample_step: null pointer");
+    if (!x_t || !cond) return fail(h, CLD_ERR_ARG, "cld_sample_step: null pointer");      // z NULL: the generator, seed 0 / step 0
     if (gd && (rc = check_guidance(h, "cld_sample_step", gd, B)) != CLD_OK) return rc;
     if (sigma_host) *sigma_host = std::exp(0.5f * h->plvc[t_idx]);
     hipStream_t s = static_cast<hipStream_t>(stream);

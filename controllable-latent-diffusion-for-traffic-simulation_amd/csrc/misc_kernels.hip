@@ -329,24 +329,28 @@ hipError_t launch_logprob(const float* xq, const float* mean, float sigma, float
 // ------------------------------------------------------------------------------------------
 // unicycle roll-out of one agent, sequential over 52 steps (the reference's tril/bmm form is an
 // O(T^2) way of writing these inclusive prefix sums; v is clipped AFTER the sum, 'parallel' mode).
+// The four running sums (v, yaw, x, y) are carried in double and rounded to float where a step reads them, as torch.cumsum carries a
+// float sum on the CPU: carried in float, 52 additions put the states up to 2x over the calibrated bar of tests/test_gpu_vae_infer.py
+// (8x the float32 oracle's own error).  Every term that is added is a float product, as in the reference.
 __device__ void rollout_agent(const DynParams& d, const float* act /*[52][2] scaled or raw*/, const float* cs,
                               float* traj /*[52][6]*/, bool scaled_input, bool descaled_output) {
-    float v_raw = cs[2], v_prev = fminf(fmaxf(cs[2], d.v_lo), d.v_hi);
-    float yaw = cs[3], x = cs[0], y = cs[1];
+    double v_raw = cs[2], yaw = cs[3], x = cs[0], y = cs[1];
+    float v_prev = fminf(fmaxf(cs[2], d.v_lo), d.v_hi);
     for (int t = 0; t < 52; ++t) {
         float acc = act[2 * t], yr = act[2 * t + 1];
         if (scaled_input) { acc = acc * d.std[4] + d.mean[4]; yr = yr * d.std[5] + d.mean[5]; }
         const float accc = fminf(fmaxf(acc, d.acc_lo), d.acc_hi);
-        v_raw += accc * d.dt;
-        const float v = fminf(fmaxf(v_raw, d.v_lo), d.v_hi);
+        v_raw += (double)(accc * d.dt);
+        const float v = fminf(fmaxf((float)v_raw, d.v_lo), d.v_hi);
         const float av = fabsf(v_prev);
         const float yb = fmaxf(fminf(d.max_steer * av, d.max_yawvel / fmaxf(av, 0.1f)), 0.1f);
         const float yrc = fmaxf(fminf(yr, yb), -yb);
         const float vavg = 0.5f * (v_prev + v);       // mat2 rows: 0.5*(v_{k-1} + v_k)
-        x += vavg * cosf(yaw) * d.dt;
-        y += vavg * sinf(yaw) * d.dt;
-        yaw += yrc * d.dt;
-        float o[6] = {x, y, v, yaw, acc, yr};
+        const float yaw_prev = (float)yaw;
+        x += (double)(vavg * cosf(yaw_prev) * d.dt);
+        y += (double)(vavg * sinf(yaw_prev) * d.dt);
+        yaw += (double)(yrc * d.dt);
+        float o[6] = {(float)x, (float)y, v, (float)yaw, acc, yr};
         if (scaled_input && !descaled_output) {
 #pragma unroll
             for (int k = 0; k < 6; ++k) o[k] = (o[k] - d.mean[k]) / d.std[k];
@@ -458,7 +462,9 @@ __global__ __launch_bounds__(256) void decode_kernel(const DecoderWeights w, con
 // v_exp_f32 / v_rcp_f32 forms (1 ulp each): ~1e-7 absolute on the gates, far inside the decode bars; the libm forms cost as
 // many cycles per step here as the 196 MFMAs do
 __device__ __forceinline__ float fsig_m(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
-__device__ __forceinline__ float ftanh_m(float x) { return 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(-2.0f * x)) - 1.0f; }
+__device__ __forceinline__ float ftanh_m(float x) { return fmaf(2.0f, __builtin_amdgcn_rcpf(1.0f + __expf(-2.0f * x)), -1.0f); }
+// The cell update below is written with fmaf: left to the compiler's contraction, the four accumulator registers of a lane (four
+// agents) got different forms (two of mul + fma, two of mul + mul + add), so an agent's result depended on its slot in the group of 16.
 
 __global__ __launch_bounds__(256) void decode_mfma_kernel(const DecoderWeights w, const DynParams d,
                                                           const float* __restrict__ z, const float* __restrict__ cond,
@@ -530,7 +536,7 @@ __global__ __launch_bounds__(256) void decode_mfma_kernel(const DecoderWeights w
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const float ig = fsig_m(acc[0][r]), fg = fsig_m(acc[1][r]), gg = ftanh_m(acc[2][r]), og = fsig_m(acc[3][r]);
-                const float c = fg * c0[r] + ig * gg;
+                const float c = fmaf(fg, c0[r], ig * gg);
                 c0[r] = c;
                 hs[0][pr ^ 1][4 * rb + r][u] = og * ftanh_m(c);
             }
@@ -553,7 +559,7 @@ __global__ __launch_bounds__(256) void decode_mfma_kernel(const DecoderWeights w
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const float ig = fsig_m(acc[0][r]), fg = fsig_m(acc[1][r]), gg = ftanh_m(acc[2][r]), og = fsig_m(acc[3][r]);
-                const float c = fg * c1[r] + ig * gg;
+                const float c = fmaf(fg, c1[r], ig * gg);
                 c1[r] = c;
                 const float hn = og * ftanh_m(c);
                 hs[1][pr ^ 1][4 * rb + r][u] = hn;
@@ -668,11 +674,17 @@ __global__ __launch_bounds__(256) void encode_kernel(const EncoderWeights w, con
         }
         __syncthreads();
         for (int t = 0; t < 52; ++t) {
-            float g = bias0;
+            // four partial sums per 64-long product (k mod 4), joined pairwise: one chain of 128 fmaf put logvar of a single row 1.4x over
+            // the calibrated bar of tests/test_gpu_vae_infer.py (10 ulp off float64 after 52 steps; four chains: a third of the bar)
+            float ga = bias0, gb = 0.f, gc = 0.f, gd = 0.f;
 #pragma unroll
-            for (int k = 0; k < 6; ++k) g = fmaf(xin[6 * t + k], wi0[k], g);
+            for (int k = 0; k < 6; ++k) ga = fmaf(xin[6 * t + k], wi0[k], ga);
 #pragma unroll
-            for (int k = 0; k < 64; ++k) g = fmaf(h0[k], wh0[k], g);
+            for (int k = 0; k < 64; k += 4) {
+                ga = fmaf(h0[k], wh0[k], ga); gb = fmaf(h0[k + 1], wh0[k + 1], gb);
+                gc = fmaf(h0[k + 2], wh0[k + 2], gc); gd = fmaf(h0[k + 3], wh0[k + 3], gd);
+            }
+            float g = (ga + gb) + (gc + gd);
             gates[r] = (gate == 2) ? tanhf(g) : sigmoid_f(g);
             __syncthreads();
             if (r < 64) {
@@ -681,11 +693,18 @@ __global__ __launch_bounds__(256) void encode_kernel(const EncoderWeights w, con
                 h0[r] = gates[192 + r] * tanhf(c);
             }
             __syncthreads();
-            g = bias1;
+            ga = bias1; gb = 0.f; gc = 0.f; gd = 0.f;
 #pragma unroll
-            for (int k = 0; k < 64; ++k) g = fmaf(h0[k], wi1[k], g);
+            for (int k = 0; k < 64; k += 4) {
+                ga = fmaf(h0[k], wi1[k], ga); gb = fmaf(h0[k + 1], wi1[k + 1], gb);
+                gc = fmaf(h0[k + 2], wi1[k + 2], gc); gd = fmaf(h0[k + 3], wi1[k + 3], gd);
+            }
 #pragma unroll
-            for (int k = 0; k < 64; ++k) g = fmaf(h1[k], wh1[k], g);
+            for (int k = 0; k < 64; k += 4) {
+                ga = fmaf(h1[k], wh1[k], ga); gb = fmaf(h1[k + 1], wh1[k + 1], gb);
+                gc = fmaf(h1[k + 2], wh1[k + 2], gc); gd = fmaf(h1[k + 3], wh1[k + 3], gd);
+            }
+            g = (ga + gb) + (gc + gd);
             gates[r] = (gate == 2) ? tanhf(g) : sigmoid_f(g);
             __syncthreads();
             if (r < 64) {
@@ -696,9 +715,12 @@ __global__ __launch_bounds__(256) void encode_kernel(const EncoderWeights w, con
             __syncthreads();
             if (r < 8) {   // mu (rows 0-3) and logvar (rows 4-7) heads on the top layer's output
                 const float* wr = (r < 4 ? w.w_mu + r * 64 : w.w_lv + (r - 4) * 64);
-                float s = (r < 4 ? w.b_mu[r] : w.b_lv[r - 4]);
-                for (int k = 0; k < 64; ++k) s = fmaf(h1[k], wr[k], s);
-                head[8 * t + r] = s;
+                float sa = (r < 4 ? w.b_mu[r] : w.b_lv[r - 4]), sb = 0.f, sc = 0.f, sd = 0.f;
+                for (int k = 0; k < 64; k += 4) {
+                    sa = fmaf(h1[k], wr[k], sa); sb = fmaf(h1[k + 1], wr[k + 1], sb);
+                    sc = fmaf(h1[k + 2], wr[k + 2], sc); sd = fmaf(h1[k + 3], wr[k + 3], sd);
+                }
+                head[8 * t + r] = (sa + sb) + (sc + sd);
             }
         }
         __syncthreads();
@@ -791,7 +813,7 @@ __global__ __launch_bounds__(256) void encode_mfma_kernel(const EncoderWeights w
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const float ig = fsig_m(acc[0][r]), fg = fsig_m(acc[1][r]), gg = ftanh_m(acc[2][r]), og = fsig_m(acc[3][r]);
-                const float c = fg * c0[r] + ig * gg;
+                const float c = fmaf(fg, c0[r], ig * gg);
                 c0[r] = c;
                 hs[0][pr ^ 1][4 * rb + r][u] = og * ftanh_m(c);
             }
@@ -819,7 +841,7 @@ __global__ __launch_bounds__(256) void encode_mfma_kernel(const EncoderWeights w
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const float ig = fsig_m(acc[0][r]), fg = fsig_m(acc[1][r]), gg = ftanh_m(acc[2][r]), og = fsig_m(acc[3][r]);
-                const float c = fg * c1[r] + ig * gg;
+                const float c = fmaf(fg, c1[r], ig * gg);
                 c1[r] = c;
                 const float hn = og * ftanh_m(c);
                 hs[1][pr ^ 1][4 * rb + r][u] = hn;

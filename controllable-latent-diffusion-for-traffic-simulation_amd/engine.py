@@ -290,6 +290,7 @@ class Engine:
         return (mse, zn) if want_z_noisy else mse
 
     def ddpm_step(self, x, cond, t_idx: int, z):
+        """DmModel.x_Tminus1 -> (x_next, mean, sigma).  z None: the noise is drawn on the device (seed 0, step 0), as by `sample_step`."""
         x = self._f32(x)
         B = x.shape[0]
         x = self._f32(x, (B, T, D)); cond = self._f32(cond, (B, COND))
@@ -653,7 +654,8 @@ class Engine:
     def sample_step(self, x_t, cond, t_idx: int, z=None, non_cond=None, guidance_w: float = 0.0, guidance: Optional[Mapping] = None,
                     want_grad: bool = False):
         """One iteration of `sample` at timestep t_idx on a given x_t (cld_sample_step; upstream p_sample, diffuser.py:844-929)
-        -> dict(x_next, mean [posterior mean before guidance], sigma, and on a guided step mean_guided [, grad])."""
+        -> dict(x_next, mean [posterior mean before guidance], sigma, and on a guided step mean_guided [, grad]).
+        z None: the step's noise is drawn on the device, as the first iteration of `sample(noise=None, seed=0)` draws it."""
         x_t = self._f32(x_t)
         B = x_t.shape[0]
         x_t = self._f32(x_t, (B, T, D)); cond = self._f32(cond, (B, COND))

@@ -124,7 +124,8 @@ int cld_denoise_loss(cld_handle h, const float* z0, const float* noise, const fl
                      float* mse, int32_t B, void* workspace, size_t workspace_bytes, void* stream);
 
 /* (x_{t-1}, mean, sigma) = DmModel.x_Tminus1(x, t, aux_info)  (dm_model.py:144-163).
- * z [B,52,4] is the caller's N(0,1) draw (the reference's randn_like, :153).
+ * z [B,52,4] is the caller's N(0,1) draw (the reference's randn_like, :153); NULL = the on-device generator as cld_sample's
+ * first iteration with seed 0 draws it (seed 0, step 0, row b * 52 + l).
  * x_next / mean [B,52,4] (either may be NULL); *sigma_host receives exp(0.5*logvar[t]). */
 int cld_ddpm_step(cld_handle h, const float* x, const float* cond, int32_t t_idx, const float* z,
                   float* x_next, float* mean, float* sigma_host /*HOST*/, int32_t B,
@@ -341,7 +342,7 @@ int cld_sample_guided(cld_handle h, const float* x_T, const float* noise, const 
  * DiffuserModel.p_sample (src/tbsim/models/diffuser.py:844-929), CLD's DmModel.x_Tminus1 (models/dm/dm_model.py:144-156) when
  * non_cond and guidance are NULL.  x_t [B,52,4] -> U-Net (twice with non_cond != NULL: eps = (1 + w) eps_c - w eps_u) ->
  * posterior mean -> [guidance step on the mean when `guidance` is given and applies at this timestep] -> x_next = mean' + sigma_t z
- * (no noise at t_idx == 0; z may then be NULL).  Outputs [B,52,4], any may be NULL: x_next; mean = the posterior mean BEFORE the
+ * (no noise at t_idx == 0; z NULL = the on-device generator with seed 0, step 0).  Outputs [B,52,4], any may be NULL: x_next; mean = the posterior mean BEFORE the
  * guidance step; mean_guided and grad = dL/dmean are written only on a guided step; *sigma_host receives sigma_t = exp(0.5 *
  * logvar[t_idx]) as the loop uses it.  Same kernels in the same order as the
  * loop: stepping through t = n-1 .. 0 with the loop's noise slabs reproduces cld_sample* bit for bit.  Workspace as for the
