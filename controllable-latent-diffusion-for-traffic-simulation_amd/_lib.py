@@ -30,6 +30,7 @@ class CldConfig(C.Structure):
 
 PRECISIONS = {"f32": 0, "f16x2": 1}
 OPTIMIZERS = {"adam": 0, "sgd": 1}
+RES_FOLD = {"fused": 0, "separate": 1}      # cld_debug_res_fold (include/cld.h CLD_RES_FOLD_*)
 KERNELS = {"guide": 0, "decode": 1, "encode": 2, "unet": 3, "context": 4, "conv5": 5}        # cld_debug_force_kernel
 # cld_debug_force_kernel: the formulations each kernel has (include/cld.h CLD_FORM_*).  The numbers are reused across kernels (3 is "quad"
 # for the guide kernel, "chain1" for the U-Net, "winograd_f2" for the ContextEncoder and "winograd_whole" for the k5 layers), so a form
@@ -143,6 +144,8 @@ SIGNATURES = {
     "cld_debug_conv5_form": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32]),
     "cld_debug_conv5_items": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.c_int32]),
     "cld_debug_unet_span": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, C.c_int32, _P, C.c_size_t, _P]),
+    "cld_debug_res_fold": (C.c_int, [_P, C.c_int32]),
+    "cld_debug_pack_res_proj": (C.c_int64, [_P, C.c_int32, C.c_int32, _P, C.c_int64]),
     "cld_debug_context_layer": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int32, C.c_int32, _P]),
     "cld_debug_context_pass_size": (C.c_int, [C.c_int32]),
     "cld_debug_stamps": (C.c_int, [_P, _P, C.c_int32]),

@@ -29,6 +29,7 @@ struct ConvLayer {
     float* ufrag = nullptr;   // Winograd-domain filters G g of a k5 layer that has a Winograd form (exact-fp32 handles): as a launch of its own
                               // (wino1d_kernels.hip: wino_launch) or inside the layer chains (chain_wino.hip: the 64 -> 64 layers at L = 52 / 26)
     bool wino_launch = false;
+    float* rfrag = nullptr;   // a block's 1x1 projection that its second conv can evaluate itself (wino1d_edge.hip): pack_res_proj
     int c_out = 0, c1_real = 0, c1_pad = 0, c2 = 0, ly = 0, off0 = 0, orow0 = 0;
     int cb_off = -1;    // offset into the 1792-wide cond/time bias rows, -1 = none
 };
@@ -89,6 +90,7 @@ struct cld_handle_s {
     unsigned long long* stamp_buf = nullptr;
     int stamp_layer = -1, launch_counter = 0;
     size_t lds_floor = 0;                // experiments (cld_debug_lds_floor)
+    int res_fold = CLD_RES_FOLD_FUSED;    // cld_debug_res_fold: the 1x1 projections inside their block's second conv, or as launches of their own
     long eval_counter = 0;               // U-Net evaluations since profile_enable: every kProfStride-th one is timed
 };
 
@@ -227,6 +229,15 @@ std::vector<float> pack_latent_conv_weights(F&& wget, int c_out) {
             for (int s = 0; s < 4; ++s) o[s] = wget(co, s, kk);
             o[4] = wget(co, kk, 4);
         }
+    return out;
+}
+
+// A residual block's 1x1 projection W [c_out][c_in] for the second conv that evaluates it (wino1d_edge.hip, ResProj::wfrag): the planes of
+// pack_conv_weights (one tap) and behind them one chunk's worth of zeros -- the kernel requests its A fragment one chunk ahead, the last
+// request included, and wino1d_edge_res_frag_floats() is both this buffer's length and the bound the kernel gives its buffer resource.
+std::vector<float> pack_res_proj(const float* W, int c_out, int c_in) {
+    std::vector<float> out = pack_conv_weights([&](int co, int ci, int) { return W[(size_t)co * c_in + ci]; }, c_out, c_in, 1);
+    out.resize((size_t)wino1d_edge_res_frag_floats(c_in, c_out), 0.f);
     return out;
 }
 
@@ -420,20 +431,25 @@ void count_launch(cld_handle h, const ConvLayer& l, int b_pad) {
     h->eval_exec_flop += exec;
     h->eval_launches++;
 }
-hipError_t launch_one(cld_handle h, const ConvLayer& l, const ConvGeom& g, const ConvArgs& a, int b_pad, hipStream_t s) {
+// rp: the block's 1x1 projection, folded into this launch (res_folds: a four-wave whole-item Winograd launch)
+hipError_t launch_one(cld_handle h, const ConvLayer& l, const ConvGeom& g, const ConvArgs& a, int b_pad, hipStream_t s, const ResProj* rp = nullptr) {
     count_launch(h, l, b_pad);
     if (use_wino1d(h, l, b_pad)) {
         ConvArgs w = a;
         w.wfrag = l.ufrag;
         w.wfrag_edge = l.ufrag_edge;
+        if (rp) {
+            w.wfrag = l.ufrag_edge;
+            return w.wfrag ? launch_wino1d_edge(w, l.g.l_in, b_pad, false, s, rp) : hipErrorInvalidValue;
+        }
         return launch_wino1d(w, l.g.l_in, b_pad, wino_item_form(h), s);
     }
-    return launch_conv(g, a, b_pad, s);
+    return rp ? hipErrorInvalidValue : launch_conv(g, a, b_pad, s);
 }
-hipError_t launch_maybe_timed(cld_handle h, const ConvLayer& l, const ConvGeom& g, const ConvArgs& a, int b_pad, hipStream_t s) {
+hipError_t launch_maybe_timed(cld_handle h, const ConvLayer& l, const ConvGeom& g, const ConvArgs& a, int b_pad, hipStream_t s, const ResProj* rp = nullptr) {
     const bool timed = h->prof_on && g.l_in == 13 && g.ntaps == 5 && g.epi == EPI_GN_MISH && l.c_out == 256 && l.c1_real == 256 &&
                        (h->eval_counter % kProfStride) == 0;
-    if (!timed) return launch_one(h, l, g, a, b_pad, s);
+    if (!timed) return launch_one(h, l, g, a, b_pad, s, rp);
     if (h->prof_used + 2 > h->prof_ev.size()) {
         for (int i = 0; i < 2; ++i) {
             hipEvent_t ev;
@@ -444,7 +460,7 @@ hipError_t launch_maybe_timed(cld_handle h, const ConvLayer& l, const ConvGeom& 
     }
     hipError_t e = hipEventRecord(h->prof_ev[h->prof_used], s);
     if (e != hipSuccess) return e;
-    e = launch_one(h, l, g, a, b_pad, s);
+    e = launch_one(h, l, g, a, b_pad, s, rp);
     if (e != hipSuccess) return e;
     e = hipEventRecord(h->prof_ev[h->prof_used + 1], s);
     h->prof_used += 2;
@@ -479,12 +495,12 @@ hipError_t run_pair(cld_handle h, const ConvLayer& la, const ConvArgs& aa, const
     return e != hipSuccess ? e : launch_maybe_timed(h, lb, gb, ab, b_pad, s);
 }
 
-hipError_t run_args(cld_handle h, const ConvLayer& l, ConvArgs a, int b_pad, hipStream_t s);
+hipError_t run_args(cld_handle h, const ConvLayer& l, ConvArgs a, int b_pad, hipStream_t s, const ResProj* rp = nullptr);
 hipError_t run_conv(cld_handle h, const ConvLayer& l, const float* x1, const float* x2, float* y, const float* res,
                     const float* cb, const float* tb_row, int b_pad, hipStream_t s) {
     return run_args(h, l, make_args(h, l, x1, x2, y, res, cb, tb_row), b_pad, s);
 }
-hipError_t run_args(cld_handle h, const ConvLayer& l, ConvArgs a, int b_pad, hipStream_t s) {
+hipError_t run_args(cld_handle h, const ConvLayer& l, ConvArgs a, int b_pad, hipStream_t s, const ResProj* rp) {
 #ifdef CLD_EXPERIMENTS
     static const int stop_after = getenv("CLD_DEBUG_STOP") ? atoi(getenv("CLD_DEBUG_STOP")) : 1 << 30;
     if (h->launch_counter >= stop_after) return hipSuccess;
@@ -493,7 +509,17 @@ hipError_t run_args(cld_handle h, const ConvLayer& l, ConvArgs a, int b_pad, hip
     h->launch_counter++;
     ConvGeom g;
     if (!pick_tiling(l, b_pad, &g)) return hipErrorInvalidValue;
-    return launch_maybe_timed(h, l, g, a, b_pad, s);
+    return launch_maybe_timed(h, l, g, a, b_pad, s, rp);
+}
+
+// Whether a residual block's second conv evaluates the block's 1x1 projection itself (wino1d_edge.hip) instead of reading the result of a
+// launch of its own: exact-fp32 handles, where that conv runs as four-wave whole Winograd items and has such an instance (blocks 2, 4 and 8;
+// block 10's second conv belongs to the tail chain).  Half items, eight-wave items and the direct form keep the separate launch.
+bool res_folds(cld_handle h, const ResBlock& rb, int b_pad) {
+    if (!rb.has_res || !rb.res.rfrag || h->precision != CLD_PRECISION_F32 || h->res_fold == CLD_RES_FOLD_SEPARATE) return false;
+    if (!use_wino1d(h, rb.c1, b_pad) || wino1d_item_form(rb.c1.g.l_in, rb.c1.c_out, b_pad, wino_item_form(h)) != 1) return false;
+    if ((long)b_pad * rb.c1.g.l_in * rb.res.c1_real * 4 >= (1L << 31)) return false;      // the kernel's 32-bit byte offsets into the block input (block 8: wider than the conv's own tensors)
+    return wino1d_edge_res_supported(rb.c1.g.l_in, rb.c1.c_out, rb.res.c1_real, rb.res.c2);
 }
 
 // The 64-channel levels as LDS-resident layer chains (conv_chain.hip): exact-fp32 handles only (the split-precision mode keeps
@@ -550,6 +576,14 @@ hipError_t run_unet_span(cld_handle h, const Ws& w, const float* x, int t_idx, i
 #define RC(...) do { e = run_conv(h, __VA_ARGS__, w.cb, tbr, b_pad, s); if (e != hipSuccess) return e; } while (0)
     auto resblock = [&](const ResBlock& rb, const float* in1, const float* in2, float* out) -> hipError_t {
         const float* r = in1;           // identity residual reads the block input
+        if (res_folds(h, rb, b_pad)) {  // the second conv projects the block input itself: no pass over it here, no tensor in b[0]
+            RC(rb.c0, in1, in2, b[1], nullptr);
+            const ResProj rp{in1, in2, rb.res.rfrag, rb.res.bias, rb.res.c1_real, rb.res.c2};
+            count_launch(h, rb.res, b_pad);      // its FLOP (the direct form's: the same MFMAs) ...
+            h->eval_launches--;                  // ... but no launch
+            h->launch_counter++;
+            return run_args(h, rb.c1, make_args(h, rb.c1, b[1], nullptr, out, nullptr, w.cb, tbr), b_pad, s, &rp);
+        }
         if (rb.has_res) {               // first conv and 1x1 projection both read only the block input: one launch
             e = run_pair(h, rb.c0, make_args(h, rb.c0, in1, in2, b[1], nullptr, w.cb, tbr),
                          rb.res, make_args(h, rb.res, in1, in2, b[0], nullptr, w.cb, tbr), b_pad, s);
@@ -780,6 +814,23 @@ int cld_debug_force_kernel(cld_handle h, int32_t which, int32_t form) {
     return CLD_OK;
 }
 
+int cld_debug_res_fold(cld_handle h, int32_t mode) {
+    if (!h || mode < CLD_RES_FOLD_FUSED || mode > CLD_RES_FOLD_SEPARATE) return fail(h, CLD_ERR_ARG, "cld_debug_res_fold: bad argument");
+    h->res_fold = mode;
+    return CLD_OK;
+}
+
+int64_t cld_debug_pack_res_proj(const float* w, int32_t c_out, int32_t c_in, float* out, int64_t capacity) {
+    if (c_out < 16 || c_out % 16 || c_in < 16 || c_in % 16) return CLD_ERR_ARG;
+    const int64_t n = wino1d_edge_res_frag_floats(c_in, c_out);
+    if (!w && !out) return n;
+    if (!w || !out || capacity < n) return CLD_ERR_ARG;
+    const std::vector<float> v = pack_res_proj(w, c_out, c_in);
+    if ((int64_t)v.size() != n) return CLD_ERR_STATE;
+    std::memcpy(out, v.data(), v.size() * sizeof(float));
+    return n;
+}
+
 int cld_debug_conv5_form(int32_t l_in, int32_t c1, int32_t c2, int32_t c_out, int64_t rows, int32_t forced_form) {
     if (l_in < 1 || c1 < 1 || c2 < 0 || c_out < 1 || rows < 0 || forced_form < 0 || forced_form > 4) return CLD_ERR_ARG;
     return conv5_takes_winograd(l_in, c1, c2, c_out, (long)((rows + 15) / 16 * 16), forced_form) ? CLD_FORM_WINOGRAD : CLD_FORM_DIRECT;
@@ -961,6 +1012,8 @@ int cld_finalize(cld_handle h, void* stream) {
         if (rb.has_res)
             if ((rc = make_conv(rb.res, p + ".residual_conv", bd.cout, c1, c2, bd.L, bd.L, 1, 1, k1, false, 0, 0, 1, bd.L,
                                 EPI_BIAS, "", latent_in)) != CLD_OK) return rc;
+        if (rb.has_res && h->precision == CLD_PRECISION_F32 && wino1d_edge_res_supported(bd.L, bd.cout, c1, c2))
+            UP(rb.res.rfrag, pack_res_proj(getw(h, p + ".residual_conv.weight")->data(), bd.cout, c1 + c2));
         if (latent_in) {      // the first block's 1x1 residual projection of the 4-channel latent runs inside its second conv's epilogue
             UP(h->res4_w, *getw(h, p + ".residual_conv.weight"));      // [64, 4, 1]
             UP(h->res4_b, *getw(h, p + ".residual_conv.bias"));

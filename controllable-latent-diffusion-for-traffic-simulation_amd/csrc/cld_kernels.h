@@ -93,8 +93,19 @@ bool wino1d_supported(int l_in, int c1, int c2, int c_out);      // c1 | c2: cha
 hipError_t launch_wino1d(const ConvArgs& a, int l_in, int b_pad, int item_form, hipStream_t s);      // item_form: 0 by size; 1 whole items, 2 whole items of eight waves, at every size (tests)
 int wino1d_item_form(int l_in, int c_out, int b_pad, int forced);   // the items a Winograd launch runs: 0 half, 1 whole, 2 whole of eight waves (forced: wino_item_form)
 long wino1d_row_planes(int l_in, int c_out, int b_pad, int item_form);   // (GEMM rows x planes) a launch of that shape and size runs: x 2 C_in C_out = the FLOP its MFMAs execute
-hipError_t launch_wino1d_edge(const ConvArgs& a, int l_in, int b_pad, bool k_split, hipStream_t s);      // wino1d_edge.hip; a.wfrag = the 12-plane fragments; k_split: eight waves per item
+// a residual block's 1x1 projection of the block input, evaluated by the block's second conv behind its Mish (wino1d_edge.hip: four-wave
+// whole items only): y = conv(x) ... + bias + W [x1 | x2]
+struct ResProj {
+    const float* x1;      // the block input [b_pad, L, c1] (and x2 [b_pad, L, c2], c2 == c1, of a concatenated input; else null)
+    const float* x2;
+    const float* wfrag;   // pack_res_proj: one plane [c_out / 16][64 lanes][4] per 16 input channels + one plane of zeros (the look-ahead)
+    const float* bias;    // [c_out]
+    int c1, c2;
+};
+hipError_t launch_wino1d_edge(const ConvArgs& a, int l_in, int b_pad, bool k_split, hipStream_t s, const ResProj* rp = nullptr);      // wino1d_edge.hip; a.wfrag = the 12-plane fragments; k_split: eight waves per item
 long wino1d_edge_row_planes(int l_in, int b_pad);
+bool wino1d_edge_res_supported(int l_in, int c_out, int rc1, int rc2);      // the second convs that have an instance with the projection folded in
+long wino1d_edge_res_frag_floats(int c_in, int c_out);      // floats of ResProj::wfrag: every offset the kernel forms, look-ahead included, lies below it
 long wino1d_gemm_rows(int l_in, int b_pad);     // GEMM rows (64 per item, idle ones included) a launch runs its 8 transform-domain products over
 void set_lds_floor(size_t bytes);      // experiments only: minimum dynamic LDS per conv launch (0 = off)
 

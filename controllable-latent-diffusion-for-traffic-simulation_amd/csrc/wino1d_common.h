@@ -81,4 +81,11 @@ __device__ __forceinline__ v4f mish4(const v4f x) {
     X(26, 64, 64, 128)          \
     X(26, 256, 128, 64)
 
+// (L, C_in, channels per source, C_out, projection C_in, its channels per source): the second convs of residual blocks 2, 4 and 8
+// (64 -> 128 @ 26, 128 -> 256 @ 13, cat(256, 256) -> 128 @ 13) with the block's 1x1 projection folded in (wino1d_edge.hip, four-wave whole items)
+#define CLD_WINO1D_RES_INSTANCES(X) \
+    X(26, 128, 128, 128, 64, 64)    \
+    X(13, 256, 256, 256, 128, 128)  \
+    X(13, 128, 128, 128, 512, 256)
+
 }  // namespace cld

@@ -22,6 +22,8 @@
 // items of [16 rows][16 channels] (64-byte rows, 16-byte slots permuted as in wino1d_kernels.hip), two images; U and the raw taps come
 // from L2 in MFMA fragment order -- 12 planes per 16-channel chunk: xi 0 .. 7, taps 0 .. 3 (cld_api.hip, ConvLayer::ufrag_edge) -- four
 // planes ahead.  No dead outputs and no idle rows: every output a lane computes is stored.
+#include <type_traits>
+
 #include "wino1d_common.h"
 
 // (wino1d_kernels.hip) a row's result must not depend on its place in the workgroup: no implicit contraction in this file
@@ -49,15 +51,65 @@ struct E1Geo {
     static_assert(NCB == 1 || NCB == 2 || NCB == 4, "XCD-aware id mapping");
 };
 
+// The residual phase's staging state (wino1d_edge_kernel, RCIN > 0).  Thread = row rr x channels 4 cq .. of the chunk, positions wave + 4 g
+// (the position of output o: 12 hh + o for o < 12, the direct column's for o = 12); wave 0 alone has a fourth position
+template <int L, int RCIN, int RCS, int NTN>
+struct ResStage {
+    static constexpr int RNCH = RCIN / 16, RNC1 = RCS / 16;
+    __amdgpu_buffer_rsrc_t rsq, rsq2, rsv;
+    int roff[4];
+    v4f q[4], rw, rbias;
+    __device__ __forceinline__ void init(const ResProj& rp, const int b_pad, const int b0, const int rr, const int cq, const int wave) {
+        const int rbytes = b_pad * L * RCS * 4;
+        rsq = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(rp.x1), 0, rbytes, 0x00020000);
+        rsq2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(RCS == RCIN ? rp.x1 : rp.x2), 0, rbytes, 0x00020000);
+        rsv = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(rp.wfrag), 0, (RNCH + 1) * NTN * 1024, 0x00020000);
+        const int a = L == 13 ? rr : rr >> 1, h2 = L == 13 ? 0 : rr & 1;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const int o = wave + 4 * g;
+            const int pos = o < 12 ? 12 * h2 + o : (L == 13 ? 12 : 24 + h2);
+            roff[g] = o < 13 ? (((b0 + a) * L + pos) * RCS + 4 * cq) * 4 : rbytes;
+        }
+    }
+    __device__ __forceinline__ void load(const int c, const int wave) {      // chunk c of the block input -> q
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            if (g == 3 && wave != 0) continue;
+            if (RCS == RCIN || c < RNC1) q[g] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(rsq, roff[g], c * 64, 0));
+            else q[g] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(rsq2, roff[g], (c - RNC1) * 64, 0));
+        }
+    }
+    __device__ __forceinline__ void store(float* img, const int wave) const {      // img: the image + this thread's place in an item
+        float* vb = img + wave * 256;
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+            if (g < 3 || wave == 0) *reinterpret_cast<v4f*>(vb + g * 1024) = q[g];
+    }
+    __device__ __forceinline__ v4f wload(const int c, const int wvoff, const int wsoff) const {      // plane c <= RNCH: inside the buffer
+        return __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(rsv, wvoff, c * (NTN * 1024) + wsoff, 0));
+    }
+};
+struct NoResStage {};
+
 }  // namespace
 
 // KS = 1: four waves, two workgroups per CU.  KS = 2 (launches of about one item per CU, where a second workgroup per CU does not exist): eight
 // waves -- waves 4 .. 7 run the second half of the input channels of the same item on V images of their own, so that every SIMD has two
 // waves and neither the staging nor the weight traffic is duplicated (the half items of wino1d_kernels.hip fetch every plane twice); their
 // accumulators meet those of waves 0 .. 3 through the LDS the images leave free after the last chunk, and waves 0 .. 3 run the epilogue alone.
-template <int L, int CIN, int CS, int COUT, int KS>
-__global__ __launch_bounds__(256 * KS, KS == 1 ? 2 : 1) void wino1d_edge_kernel(const ConvArgs p, const int b_pad, const int xcd_map) {
+//
+// RCIN > 0 (KS = 1): the residual block's 1x1 projection of the block input (RCIN channels, RCS per source) runs behind the Mish instead of
+// as a launch of its own whose result the epilogue reads back: a lane's 13 outputs ARE the C tiles (16 channels x 16 rows, one per output
+// position) of W_res x, so they go on as accumulators.  Per 16-channel chunk of the block input the 256 threads copy its 13 positions x 16
+// rows into the V images the main loop has left (items 0 .. 12 of an image, the direct column's row layout; wave w: positions w, w + 4,
+// w + 8 and, wave 0, 12), two images in turn with one barrier per chunk; a wave then issues 13 x 4 MFMAs with ONE A fragment (its 16
+// output channels x the chunk, rp.wfrag, one chunk ahead -- the buffer ends on a plane of zeros).  A 1x1 projection reads no padding: every
+// row it asks for exists.
+template <int L, int CIN, int CS, int COUT, int KS, int RCIN = 0, int RCS = 0>
+__global__ __launch_bounds__(256 * KS, KS == 1 ? 2 : 1) void wino1d_edge_kernel(const ConvArgs p, const int b_pad, const int xcd_map, const ResProj rp) {
     typedef E1Geo<L, CIN, CS, COUT> G;
+    static_assert(RCIN == 0 || (KS == 1 && RCIN % 32 == 0 && (RCS == RCIN || 2 * RCS == RCIN)), "the projection: four-wave items, chunk pairs, one source or two equal ones");
     extern __shared__ __attribute__((aligned(16))) float lds1[];
     constexpr int VB = G::VB;
     float* xch = lds1 + 2 * KS * VB;
@@ -250,7 +302,7 @@ __global__ __launch_bounds__(256 * KS, KS == 1 ? 2 : 1) void wino1d_edge_kernel(
     const int ybytes = b_pad * L * COUT * 4;
     const __amdgpu_buffer_rsrc_t rsy = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, ybytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.res ? p.res : p.y), 0, ybytes, 0x00020000);
-    const bool has_res = p.res != nullptr;
+    const bool has_res = RCIN == 0 && p.res != nullptr;
     const int b = b0 + (L == 13 ? i16 : i16 >> 1), hh = L == 13 ? 0 : i16 & 1;
     // (the distances between a row's outputs go into the VECTOR offset: with them in the scalar offset operand of the 16-byte stores, whose
     //  data registers the next output reuses, lanes 12 .. 15 of every 16 stored the next output's values -- measured on gfx950)
@@ -261,6 +313,14 @@ __global__ __launch_bounds__(256 * KS, KS == 1 ? 2 : 1) void wino1d_edge_kernel(
 #pragma unroll
         for (int o = 0; o < 12; ++o) rv[o] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(rsr, obase + o * (COUT * 4), 0, 0));
         rv[12] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(rsr, odir, 0, 0));
+    }
+    // the projection's state (RCIN > 0 only: the other instances hold an empty object and none of its code)
+    [[maybe_unused]] std::conditional_t<(RCIN > 0), ResStage<L, RCIN, RCS, G::NTN>, NoResStage> rs;
+    if constexpr (RCIN > 0) {
+        rs.init(rp, b_pad, b0, rr, cq, wave);
+        rs.load(0, wave);
+        rs.rw = rs.wload(0, wvoff, wsoff);
+        rs.rbias = *reinterpret_cast<const v4f*>(rp.bias + n4);
     }
     v4f cbv = {0.f, 0.f, 0.f, 0.f};
     if (p.cbias) cbv = *reinterpret_cast<const v4f*>(p.cbias + (size_t)b * p.cb_stride + n4);
@@ -316,12 +376,52 @@ __global__ __launch_bounds__(256 * KS, KS == 1 ? 2 : 1) void wino1d_edge_kernel(
         const v4f sc = (1.0f / sqrtf(s2 * inv + 1e-5f)) * gam;
         const v4f sh = __builtin_elementwise_fma(sc, v4f{-mean, -mean, -mean, -mean}, bet);
         const v4f add = tb + cbv;
+        if constexpr (RCIN == 0) {
 #pragma unroll
         for (int o = 0; o < 13; ++o) {
             v4f v = mish4(__builtin_elementwise_fma(Y[o], sc, sh)) + add;
             if (has_res) v += rv[o];
             if (o < 12) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4v, v), rsy, obase + o * (COUT * 4), 0, 0);
             else __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4v, v), rsy, odir, 0, 0);
+        }
+        } else {
+            constexpr int RNCH = RCIN / 16;
+            rs.store(lds1 + wofs, wave);       // (the images are dead: the main loop ended on a barrier)
+#pragma unroll
+            for (int o = 0; o < 13; ++o) Y[o] = (mish4(__builtin_elementwise_fma(Y[o], sc, sh)) + add) + rs.rbias;
+            __syncthreads();
+            // chunk c: image c & 1 holds its rows; the next chunk's rows and A fragment are requested first and stored behind the MFMAs
+            auto res_block = [&](const int buf, const int c, const bool stage) {
+                const v4f wcur = rs.rw;
+                rs.rw = rs.wload(c + 1, wvoff, wsoff);
+                if (stage) rs.load(c + 1, wave);
+                const int bo = buf * (VB * 4);
+                auto frag = [&](const int it) { return *reinterpret_cast<const v4f*>(ldsb + abase + bo + it * 1024); };
+                v4f ar[3];
+                ar[0] = frag(0);
+                ar[1] = frag(1);
+#pragma unroll
+                for (int o = 0; o < 13; ++o) {
+                    if (o + 2 < 13) ar[(o + 2) % 3] = frag(o + 2);
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) Y[o] = __builtin_amdgcn_mfma_f32_16x16x4f32(wcur[e], ar[o % 3][e], Y[o], 0, 0, 0);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                if (stage) rs.store(lds1 + (buf ^ 1) * VB + wofs, wave);
+            };
+#pragma clang loop unroll(disable)
+            for (int c = 0; c < RNCH; c += 2) {
+                res_block(0, c, true);
+                __syncthreads();
+                res_block(1, c + 1, c + 2 < RNCH);
+                __syncthreads();
+            }
+#pragma unroll
+            for (int o = 0; o < 13; ++o) {
+                if (o < 12) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4v, Y[o]), rsy, obase + o * (COUT * 4), 0, 0);
+                else __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4v, Y[o]), rsy, odir, 0, 0);
+            }
         }
     }
     W1STAMP(4);
@@ -345,14 +445,46 @@ static hipError_t launch_wino1d_edge_inst(const ConvArgs& a, int b_pad, bool k_s
     if (hipError_t e = set_max_lds_once(reinterpret_cast<const void*>(kern2), (int)lds2, &attr_done2); e != hipSuccess) return e;
     if ((long)b_pad * L * CS * 4 >= (1L << 31) || (long)b_pad * L * COUT * 4 >= (1L << 31)) return hipErrorInvalidValue;      // byte offsets are 32-bit
     const int groups = b_pad / G::AG;
-    if (k_split) hipLaunchKernelGGL(kern2, dim3(groups * G::NCB), dim3(512), lds2, s, a, b_pad, groups % 8 == 0 ? 1 : 0);
-    else hipLaunchKernelGGL(kern, dim3(groups * G::NCB), dim3(256), G::LDS_BYTES, s, a, b_pad, groups % 8 == 0 ? 1 : 0);
+    if (k_split) hipLaunchKernelGGL(kern2, dim3(groups * G::NCB), dim3(512), lds2, s, a, b_pad, groups % 8 == 0 ? 1 : 0, ResProj{});
+    else hipLaunchKernelGGL(kern, dim3(groups * G::NCB), dim3(256), G::LDS_BYTES, s, a, b_pad, groups % 8 == 0 ? 1 : 0, ResProj{});
     return hipGetLastError();
 }
 
+// the four-wave whole items with the block's 1x1 projection folded in
+template <int L, int CIN, int CS, int COUT, int RCIN, int RCS>
+static hipError_t launch_wino1d_edge_res_inst(const ConvArgs& a, const ResProj& rp, int b_pad, hipStream_t s) {
+    typedef E1Geo<L, CIN, CS, COUT> G;
+    auto kern = wino1d_edge_kernel<L, CIN, CS, COUT, 1, RCIN, RCS>;
+    static unsigned long long attr_done = 0;      // one bit per device
+    if (hipError_t e = set_max_lds_once(reinterpret_cast<const void*>(kern), (int)G::LDS_BYTES, &attr_done); e != hipSuccess) return e;
+    if ((long)b_pad * L * CS * 4 >= (1L << 31) || (long)b_pad * L * COUT * 4 >= (1L << 31) || (long)b_pad * L * RCS * 4 >= (1L << 31)) return hipErrorInvalidValue;      // byte offsets are 32-bit
+    const int groups = b_pad / G::AG;
+    hipLaunchKernelGGL(kern, dim3(groups * G::NCB), dim3(256), G::LDS_BYTES, s, a, b_pad, groups % 8 == 0 ? 1 : 0, rp);
+    return hipGetLastError();
+}
+
+bool wino1d_edge_res_supported(int l_in, int c_out, int rc1, int rc2) {
+#define X(L, CIN, CS, COUT, RCIN, RCS) \
+    if (l_in == L && c_out == COUT && CIN == COUT && rc1 == RCS && rc1 + rc2 == RCIN) return true;
+    CLD_WINO1D_RES_INSTANCES(X)
+#undef X
+    return false;
+}
+
+long wino1d_edge_res_frag_floats(int c_in, int c_out) { return (long)(c_in / 16 + 1) * (c_out / 16) * 256; }      // the kernel's buffer bound: (RNCH + 1) planes of NTN x 1,024 bytes
+
 // a.wfrag: the 12-plane fragments (ConvLayer::ufrag_edge)
-hipError_t launch_wino1d_edge(const ConvArgs& a, int l_in, int b_pad, bool k_split, hipStream_t s) {
+hipError_t launch_wino1d_edge(const ConvArgs& a, int l_in, int b_pad, bool k_split, hipStream_t s, const ResProj* rp) {
     if (b_pad < 16 || b_pad % 16 || a.res4_x || a.c1_real != a.c1_pad || (a.c2 != 0) != (a.x2 != nullptr)) return hipErrorInvalidValue;
+    if (rp) {      // a missing instance is an error, never a launch without the projection
+        if (k_split || a.res || !rp->x1 || !rp->wfrag || !rp->bias || (rp->c2 != 0) != (rp->x2 != nullptr)) return hipErrorInvalidValue;
+#define X(L, CIN, CS, COUT, RCIN, RCS) \
+        if (l_in == L && a.c1_real == CS && a.c1_real + a.c2 == CIN && a.c_out == COUT && rp->c1 == RCS && rp->c1 + rp->c2 == RCIN) \
+            return launch_wino1d_edge_res_inst<L, CIN, CS, COUT, RCIN, RCS>(a, *rp, b_pad, s);
+        CLD_WINO1D_RES_INSTANCES(X)
+#undef X
+        return hipErrorInvalidValue;
+    }
 #define X(L, CIN, CS, COUT) \
     if (l_in == L && a.c1_real == CS && a.c1_real + a.c2 == CIN && a.c_out == COUT) return launch_wino1d_edge_inst<L, CIN, CS, COUT>(a, b_pad, k_split, s);
     CLD_WINO1D_INSTANCES(X)

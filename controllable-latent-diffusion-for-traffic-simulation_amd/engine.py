@@ -152,6 +152,13 @@ class Engine:
             raise CldError(f"force_kernel: {ex}") from None
         self._check(self.lib.cld_debug_force_kernel(self._h, _lib.KERNELS[which], fid), "cld_debug_force_kernel")
 
+    def res_fold(self, mode: str = "fused"):
+        """Tests only (cld_debug_res_fold): the 1x1 residual projections of spans 1, 4 and 8 inside their block's second conv ("fused":
+        wherever that conv runs four-wave whole Winograd items: the default) or as launches of their own ("separate")."""
+        if mode not in _lib.RES_FOLD:
+            raise CldError(f"res_fold: unknown mode '{mode}' (one of {sorted(_lib.RES_FOLD)})")
+        self._check(self.lib.cld_debug_res_fold(self._h, _lib.RES_FOLD[mode]), "cld_debug_res_fold")
+
     def debug_unet_span(self, span: int, x1, cond, t, x2=None):
         """Tests only (cld_debug_unet_span): span `span` (0..11) of a U-Net evaluation, the same launches `unet_forward` makes for it
         in the form `force_kernel("unet" / "conv5", ...)` holds.  x1 [B, L, C] (span 0: the latent [B,52,4]); x2 the skip [B, L, C]

@@ -466,6 +466,22 @@ int cld_debug_conv5_form(int32_t l_in, int32_t c1, int32_t c2, int32_t c_out, in
  * cld_debug_conv5_form's answer.  < 0: bad argument. */
 int cld_debug_conv5_items(int32_t l_in, int32_t c_out, int64_t rows, int32_t forced_form);
 
+/* Tests only: where the 1x1 residual projection of the blocks downs.1.0, downs.2.0 and ups.0.0 (spans 1, 4, 8) is evaluated on this handle.
+ * Their second Conv1d(k5) + GroupNorm + Mish launch evaluates it itself, behind its Mish, wherever that launch runs four-wave whole
+ * Winograd items (cld_debug_conv5_items == 1; exact-fp32 handles; every tensor below the kernel's 2 GiB of 32-bit byte offsets):
+ * CLD_RES_FOLD_FUSED, the default, every such launch; CLD_RES_FOLD_SEPARATE none -- the projection is then a launch of its own next to
+ * the block's first conv, as it is in every other form.  With cld_debug_force_kernel(CLD_KERNEL_CONV5, CLD_FORM_WINOGRAD_WHOLE) both forms
+ * exist at every batch size. */
+#define CLD_RES_FOLD_FUSED 0
+#define CLD_RES_FOLD_SEPARATE 1
+int cld_debug_res_fold(cld_handle h, int32_t mode);
+
+/* The weights W [c_out][c_in] (HOST) of such a projection in the order the fused launch reads them (no handle, no device call; tests): per 16
+ * input channels one plane [c_out / 16][64 lanes][4] = W[16 nt + (lane & 15)][16 chunk + 4 (lane >> 4) + s], and behind the last one plane of
+ * zeros, which the kernel's one-chunk look-ahead lands on.  Returns the number of floats -- the bound the kernel gives its buffer resource
+ * -- and fills out[0 .. n) (HOST, `capacity` floats); with w and out NULL only the size.  < 0: bad argument. */
+int64_t cld_debug_pack_res_proj(const float* w, int32_t c_out, int32_t c_in, float* out, int64_t capacity);
+
 /* One of the 12 spans a U-Net evaluation is run as (tests): the same launches cld_unet_forward makes for that span, in the form
  * cld_debug_force_kernel(CLD_KERNEL_UNET / CLD_KERNEL_CONV5, ...) holds.  Spans (input -> output per agent, [L, C] row-major):
  *   0 downs.0.* [52,4] -> [26,64]; 1 downs.1.0 -> [26,128]; 2 downs.1.1 -> [26,128]; 3 downs.1.2 -> [13,128]; 4 downs.2.0 -> [13,256];

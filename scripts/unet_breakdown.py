@@ -22,6 +22,10 @@ def split_pair(tag, mac, res_mac):
     return [(tag.split("+res")[0] + " (k5, Winograd)" + tag.split("+res")[1], mac - res_mac), (tag.split("+res")[0].split(".")[0] + ".res 1x1" + tag.split("+res")[1], res_mac)]
 LW = [LC[0]] + split_pair(*LC[1], 212992) + LC[2:6] + split_pair(*LC[6], 425984) + LC[7:14] + split_pair(*LC[14], 851968) + LC[15:19] + \
      split_pair(*LC[19], 425984) + LC[20:]
+# with a block's 1x1 projection folded into its second conv (wino1d_edge.hip, four-wave whole items: blocks 2, 4 and 8 at 4,096 rows)
+def fold(res, c1):
+    return (c1[0] + " + " + res[0].split()[0] + " folded in", res[1] + c1[1])
+LF = LW[:2] + [fold(LW[2], LW[3])] + LW[4:8] + [fold(LW[8], LW[9])] + LW[10:17] + [fold(LW[17], LW[18])] + LW[19:]
 path, B = sys.argv[1], int(sys.argv[2])
 rows = [r for r in csv.DictReader(open(path)) if "cld::" in r["Kernel_Name"]]
 rows.sort(key=lambda r: int(r["Start_Timestamp"]))
@@ -36,7 +40,7 @@ evals = [ev for ev in evals if len(ev) == len(evals[-1])][-8:]
 assert evals, "no complete U-Net evaluation in the trace"
 nl = len(evals[-1])
 if any("chain_" in r["Kernel_Name"] for r in evals[-1]):
-    L = LW if nl == len(LW) else LC
+    L = LW if nl == len(LW) else LF if nl == len(LF) else LC
 labelled = nl == len(L)          # below ~2,048 rows some pairs run as two launches (their tilings differ): no per-launch FLOP then
 tot_t = 0.0
 tot_f = 2.0 * sum(m for _, m in L) * B
