@@ -94,6 +94,15 @@ class CldGoal(C.Structure):
                 ("num_samp", C.c_int32), ("global_t", C.c_int32), ("dt", C.c_float), ("min_progress_dist", C.c_float)]
 
 
+class CldRaster(C.Structure):
+    """include/cld.h `cld_raster` (the scene an observation raster is built from, device pointers)."""
+    _fields_ = [("hist_world", C.c_void_p), ("hist_avail", C.c_void_p), ("scene_start", C.c_void_p), ("maps", C.c_void_p),
+                ("scene_map", C.c_void_p), ("map_from_world", C.c_void_p),
+                ("num_scenes", C.c_int32), ("B_all", C.c_int32), ("T_hist", C.c_int32), ("n_sem", C.c_int32), ("height", C.c_int32),
+                ("width", C.c_int32), ("num_maps", C.c_int32), ("map_h", C.c_int32), ("map_w", C.c_int32),
+                ("px_per_m", C.c_float), ("ego_center", C.c_float * 2), ("no_map_fill", C.c_float), ("max_neighbor_dist", C.c_float)]
+
+
 GOAL_KINDS = {"global_target_pos": 1, "global_target_pos_at_time": 2}      # cld_goal.kind (0 = off)
 
 _P = C.c_void_p
@@ -135,6 +144,7 @@ SIGNATURES = {
     "cld_goal_loss": (C.c_int, [_P, _P, C.POINTER(CldGoal), _P, _P, _P, C.c_int32, _P]),
     "cld_set_goal_term": (C.c_int, [_P, C.POINTER(CldGoal)]),
     "cld_world_step": (C.c_int, [_P, _P, _P, _P, C.c_int32, _P, _P, C.c_int32, _P]),
+    "cld_rasterize": (C.c_int, [_P, C.POINTER(CldRaster), C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "cld_profile_enable": (C.c_int, [_P, C.c_int32]),
     "cld_profile_read": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
     "cld_profile_read_executed": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32)]),

@@ -2028,6 +2028,33 @@ int cld_world_step(cld_handle h, const float* traj, const float* centroid, const
     return CLD_OK;
 }
 
+int cld_rasterize(cld_handle h, const cld_raster* r, int32_t row0, int32_t B, float* image, uint8_t* drivable, float* raster_from_world,
+                  void* stream) {
+    if (!h) return CLD_ERR_ARG;
+    if (!r || !image || !r->hist_world || !r->hist_avail || !r->scene_start) return fail(h, CLD_ERR_ARG, "cld_rasterize: null argument");
+    if (r->num_scenes < 1 || r->B_all < 1 || r->B_all > CLD_RASTER_MAX_AGENTS || r->T_hist < 1 || r->T_hist > CLD_RASTER_MAX_PLANES ||
+        r->n_sem < 0 || r->n_sem > CLD_RASTER_MAX_PLANES)
+        return fail(h, CLD_ERR_ARG, "cld_rasterize: num_scenes / B_all / T_hist / n_sem out of range (include/cld.h CLD_RASTER_MAX_*)");
+    if (B < 1 || row0 < 0 || (int64_t)row0 + B > r->B_all) return fail(h, CLD_ERR_ARG, "cld_rasterize: rows [row0, row0 + B) are not within B_all");
+    if (r->height < 1 || r->width < 1 || (int64_t)r->height * r->width > CLD_RASTER_MAX_PIXELS)
+        return fail(h, CLD_ERR_ARG, "cld_rasterize: height x width out of range (include/cld.h CLD_RASTER_MAX_PIXELS)");
+    if (!(r->px_per_m > 0.f)) return fail(h, CLD_ERR_ARG, "cld_rasterize: px_per_m must be positive");
+    if (r->maps && (!r->scene_map || !r->map_from_world || r->num_maps < 1 || r->map_h < 1 || r->map_w < 1 || r->n_sem < 1 ||
+                    (int64_t)r->map_h * r->map_w > INT32_MAX))
+        return fail(h, CLD_ERR_ARG, "cld_rasterize: maps need scene_map, map_from_world, num_maps, map_h, map_w and n_sem");
+    if (drivable && r->n_sem < 1) return fail(h, CLD_ERR_ARG, "cld_rasterize: the drivable map is the first semantic plane (n_sem >= 1)");
+    if ((int64_t)B * (r->T_hist + r->n_sem) > INT32_MAX) return fail(h, CLD_ERR_ARG, "cld_rasterize: too many planes for one launch");
+    RasterArgs a{};
+    a.hist_world = r->hist_world; a.hist_avail = r->hist_avail; a.scene_start = r->scene_start; a.maps = r->maps; a.scene_map = r->scene_map;
+    a.map_from_world = r->map_from_world; a.image = image; a.drivable = drivable; a.raster_from_world = raster_from_world;
+    a.num_scenes = r->num_scenes; a.B_all = r->B_all; a.T = r->T_hist; a.n_sem = r->n_sem; a.H = r->height; a.W = r->width;
+    a.num_maps = r->num_maps; a.map_h = r->map_h; a.map_w = r->map_w; a.row0 = row0; a.B = B;
+    a.ppm = r->px_per_m; a.ox = (1.f + r->ego_center[0]) * 0.5f * (float)r->width; a.oy = (1.f + r->ego_center[1]) * 0.5f * (float)r->height;
+    a.fill = r->no_map_fill; a.max_dist = r->max_neighbor_dist;
+    HIPCK(h, launch_raster(a, static_cast<hipStream_t>(stream)));
+    return CLD_OK;
+}
+
 /* ---- training: what the U-Net and the LSTM-VAE entry points share ---- */
 static int param_info(cld_handle h, const char* fn, const TrainParam* table, int count, int32_t i, const char** name, size_t* offset,
                       size_t* numel, int32_t* shape, int32_t* ndim) {

@@ -263,6 +263,25 @@ hipError_t launch_state_to_state_action(const DynParams& d, const float* pos, co
 hipError_t launch_world_step(const float* traj, const float* centroid, const float* yaw, int k, float* world,
                              float* next_cs, int B, hipStream_t s);
 
+// the observation raster of the closed loop (raster_kernels.hip; src/tbsim/utils/trajdata_utils.py:123-156, 381-420): history planes
+// painted from the scene's world-frame histories, semantic planes sampled from the scene's map, for rows [row0, row0 + B)
+struct RasterArgs {
+    const float* hist_world;          // [B_all, T, 3] world x, y, yaw; frame T - 1 = now
+    const unsigned char* hist_avail;  // [B_all, T]
+    const int* scene_start;           // [num_scenes + 1]
+    const float* maps;                // [num_maps, n_sem, map_h, map_w] or null
+    const int* scene_map;             // [num_scenes], < 0: no map (read only when maps != null)
+    const float* map_from_world;      // [num_maps, 3, 3]
+    float* image;                     // [B, T + n_sem, H, W]
+    unsigned char* drivable;          // [B, H, W] or null
+    float* raster_from_world;         // [B, 3, 3] or null
+    int num_scenes, B_all, T, n_sem, H, W, num_maps, map_h, map_w, row0, B;
+    float ppm, ox, oy, fill, max_dist;
+    int vec;                          // set by the launcher: 16-byte stores are possible
+};
+size_t raster_lds_bytes(int H, int W);
+hipError_t launch_raster(const RasterArgs& a, hipStream_t s);
+
 // ---- ContextEncoder (models/context_utils.py:8-61; context_kernels.hip) ------------------------------------
 // stem: image [B,34,224,224] NCHW -> y [B,112,112,64] NHWC = ReLU(BN(conv 7x7/2)); wq: packed by pack_stem_weights
 // pooled != null: MaxPool2d(3, 2, 1) fused (y unused): pooled [B,56,56,64] NHWC, zero-filled by the launcher, completed by atomic max

@@ -943,6 +943,63 @@ class Engine:
                                                 _ptr(ncs), B, self._stream()), "cld_world_step")
         return world, ncs
 
+    def rasterize(self, hist_world, hist_avail, scene_start, maps=None, scene_map=None, map_from_world=None, row0: int = 0,
+                  B: Optional[int] = None, height: int = 224, width: int = 224, px_per_m: float = 2.0, ego_center=(-0.5, 0.0),
+                  no_map_fill: float = -1.0, max_neighbor_dist: float = 30.0, n_sem: int = 3, out=None, want_drivable: bool = True,
+                  want_raster_from_world: bool = True):
+        """The observation raster of rows [row0, row0 + B) of a scene set (cld_rasterize; include/cld.h for the definition):
+        hist_world [B_all,T,3] world (x, y, yaw), oldest first, frame T - 1 = now; hist_avail [B_all,T]; scene_start [num_scenes + 1]
+        (int32, the device-side convention of agent_collision); maps [num_maps,n_sem,map_h,map_w] with scene_map [num_scenes] (< 0: no
+        map) and map_from_world [num_maps,3,3], or None.  Tensors already on the device in the right type are read in place.
+        -> (image [B,T+n_sem,H,W], drivable_map [B,H,W] uint8 | None, raster_from_world [B,3,3] | None); `out`: an image buffer to
+        reuse (its first B rows are written and returned)."""
+        hw = self._f32(hist_world)
+        if hw.dim() != 3 or hw.shape[2] != 3:
+            raise CldError(f"rasterize: hist_world must be [B_all,T,3], got {tuple(hw.shape)}")
+        B_all, Th = int(hw.shape[0]), int(hw.shape[1])
+        av = torch.as_tensor(hist_avail)
+        if not (av.dtype == torch.uint8 and av.device == self.device):
+            av = (av != 0).to(self.device, torch.uint8)
+        av = av.contiguous()
+        if tuple(av.shape) != (B_all, Th):
+            raise CldError(f"rasterize: hist_avail must be [{B_all},{Th}], got {tuple(av.shape)}")
+        ss = torch.as_tensor(scene_start).to(self.device, torch.int32).contiguous()
+        if ss.dim() != 1 or ss.numel() < 2:
+            raise CldError("rasterize: scene_start must be [num_scenes + 1]")
+        S = int(ss.numel()) - 1
+        B = B_all - int(row0) if B is None else int(B)
+        mp = sm = mfw = None
+        num_maps = map_h = map_w = 0
+        if maps is not None:
+            mp = self._f32(maps)
+            if mp.dim() != 4 or mp.shape[1] != n_sem:
+                raise CldError(f"rasterize: maps must be [num_maps,{n_sem},map_h,map_w], got {tuple(mp.shape)}")
+            num_maps, map_h, map_w = int(mp.shape[0]), int(mp.shape[2]), int(mp.shape[3])
+            if scene_map is None or map_from_world is None:
+                raise CldError("rasterize: maps need scene_map and map_from_world")
+            sm = torch.as_tensor(scene_map).to(self.device, torch.int32).contiguous()
+            if tuple(sm.shape) != (S,):
+                raise CldError(f"rasterize: scene_map must be [{S}], got {tuple(sm.shape)}")
+            mfw = self._f32(map_from_world, (num_maps, 3, 3))
+        C_ = Th + int(n_sem)
+        if out is None:
+            image = torch.empty(max(B, 0), C_, int(height), int(width), dtype=torch.float32, device=self.device)
+        else:
+            if not (out.dtype == torch.float32 and out.device == self.device and out.is_contiguous() and out.dim() == 4
+                    and out.shape[0] >= B and tuple(out.shape[1:]) == (C_, int(height), int(width))):
+                raise CldError(f"rasterize: out must be a contiguous float32 [>= {B},{C_},{height},{width}] on {self.device}")
+            image = out[:B]
+        drv = torch.empty(max(B, 0), int(height), int(width), dtype=torch.uint8, device=self.device) if want_drivable else None
+        rfw = torch.empty(max(B, 0), 3, 3, dtype=torch.float32, device=self.device) if want_raster_from_world else None
+        dp = lambda t: None if t is None else t.data_ptr()
+        rs = _lib.CldRaster(hw.data_ptr(), av.data_ptr(), ss.data_ptr(), dp(mp), dp(sm), dp(mfw), S, B_all, Th, int(n_sem),
+                            int(height), int(width), num_maps, map_h, map_w, float(px_per_m),
+                            (C.c_float * 2)(float(ego_center[0]), float(ego_center[1])), float(no_map_fill), float(max_neighbor_dist))
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cld_rasterize(self._h, C.byref(rs), int(row0), B, _ptr(image), _ptr(drv), _ptr(rfw), self._stream()),
+                        "cld_rasterize")
+        return image, drv, rfw
+
     # ------------------------------------------------------------------ measurement
     def profile_enable(self, on: bool = True):
         self._check(self.lib.cld_profile_enable(self._h, int(on)), "cld_profile_enable")

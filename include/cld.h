@@ -453,6 +453,46 @@ int cld_guidance_losses(cld_handle h, const float* traj, const cld_guidance* gui
 int cld_world_step(cld_handle h, const float* traj, const float* centroid, const float* yaw, int32_t k, float* world,
                    float* next_curr_states, int32_t B, void* stream);
 
+/* The observation of the closed loop, built on the device from the scene: data_batch['image'] as upstream's parse_node_centric ->
+ * rasterize_agents make it (src/tbsim/utils/trajdata_utils.py:123-156, 381-420), for rows [row0, row0 + B) of a scene set of B_all agents
+ * (the rows of one rank; the histories cover every rank's agents).  Needs no weights.  For row r with pose (x, y, h) = hist_world[r, T_hist-1]:
+ *   raster_from_agent = [[ppm, 0, (1 + ego_center[0]) / 2 * width], [0, ppm, (1 + ego_center[1]) / 2 * height], [0, 0, 1]]
+ *   (config.yaml:81-86: ppm 2, ego_center (-0.5, 0), 224 x 224 -> offsets 56, 112).
+ *   History planes t = 0 .. T_hist-1 (oldest first), rasterize_agents as written: a position goes to the agent frame, R(-h) (p - p_r), then
+ *   through raster_from_agent, in fp32; an unavailable frame takes the raster position (0, 0); x is clamped to [0, width-1], y to
+ *   [0, height-1], then rounded half to even; neighbours paint -1, the ego paints +1 on top; flat pixels 0 and height*width-1 are then set
+ *   to 0.  A neighbour outside the raster therefore paints a border pixel (upstream's behaviour, kept).  Yaw is not drawn.
+ *   Neighbours of r: the agents j != r of r's scene (scene_start, as in cld_collision) with hist_avail[j, T_hist-1] set and a current world
+ *   distance <= max_neighbor_dist (config.yaml:96: 30; <= 0: the whole scene); each paints its own available frames.  This rule stands in for
+ *   trajdata's neighbour selection, which is not part of the reference tree: PARITY UNPINNED.
+ *   Semantic planes T_hist .. T_hist+n_sem-1, pixel (u, v): agent point ((u - ox) / ppm, (v - oy) / ppm), world point p_r + R(h) . it, map
+ *   pixel rint(map_from_world[m] . world point), m = scene_map[scene]; value maps[m, layer, y, x] inside the map, else no_map_fill; every
+ *   plane is no_map_fill when maps == NULL or m < 0.  Nearest-pixel sampling is this library's definition (trajdata's patch code is not part
+ *   of the reference tree): PARITY UNPINNED.
+ *   drivable [B, height, width] bytes = (plane T_hist != 0), upstream's .bool() of the drivable layer (trajdata_utils.py:185-196): fill
+ *   pixels count as drivable.  raster_from_world [B,3,3] = raster_from_agent . agent_from_world.
+ * Limits (CLD_ERR_ARG beyond them; nothing is skipped silently): a scene may hold any number of the B_all agents -- the neighbour loop
+ * strides over the scene -- with B_all <= CLD_RASTER_MAX_AGENTS; height * width <= CLD_RASTER_MAX_PIXELS (the two paint masks of a plane
+ * live in LDS); T_hist, n_sem <= CLD_RASTER_MAX_PLANES.  16-byte stores when height * width is a multiple of 4 and image is 16-byte
+ * aligned (drivable 4-byte), dword stores otherwise.  The ContextEncoder itself still requires 34 x 224 x 224. */
+#define CLD_RASTER_MAX_AGENTS (1 << 24)
+#define CLD_RASTER_MAX_PIXELS (1 << 17)
+#define CLD_RASTER_MAX_PLANES 1024
+typedef struct cld_raster {
+    const float*   hist_world;      /* DEVICE [B_all, T_hist, 3] world x, y, yaw; oldest first, frame T_hist-1 = now */
+    const uint8_t* hist_avail;      /* DEVICE [B_all, T_hist] */
+    const int32_t* scene_start;     /* DEVICE [num_scenes + 1] */
+    const float*   maps;            /* DEVICE [num_maps, n_sem, map_h, map_w] or NULL */
+    const int32_t* scene_map;       /* DEVICE [num_scenes], < 0: no map */
+    const float*   map_from_world;  /* DEVICE [num_maps, 3, 3] */
+    int32_t num_scenes, B_all, T_hist, n_sem, height, width, num_maps, map_h, map_w;
+    float   px_per_m, ego_center[2], no_map_fill, max_neighbor_dist;
+} cld_raster;
+
+int cld_rasterize(cld_handle h, const cld_raster* r, int32_t row0, int32_t B,
+                  float* image /*[B, T_hist+n_sem, H, W]*/, uint8_t* drivable /*[B,H,W] or NULL*/,
+                  float* raster_from_world /*[B,3,3] or NULL*/, void* stream);
+
 /* Which form a Conv1d(k5) + GroupNorm + Mish launch takes (no handle, no device call; tests): CLD_FORM_WINOGRAD or CLD_FORM_DIRECT for a
  * layer with `c1` (+ `c2` concatenated) input channels, `c_out` output channels and `l_in` rows per agent in a launch set of `rows` agents
  * (padded to 16 inside), with `forced_form` = what cld_debug_force_kernel(CLD_KERNEL_CONV5, ...) would hold (CLD_FORM_AUTO: by size).
