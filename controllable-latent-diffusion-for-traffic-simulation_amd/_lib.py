@@ -103,6 +103,19 @@ class CldRaster(C.Structure):
                 ("px_per_m", C.c_float), ("ego_center", C.c_float * 2), ("no_map_fill", C.c_float), ("max_neighbor_dist", C.c_float)]
 
 
+class CldSceneMetrics(C.Structure):
+    """include/cld.h `cld_scene_metrics` (the scene set the closed-loop episode metrics are computed over, device pointers)."""
+    _fields_ = [("extent", C.c_void_p), ("scene_start", C.c_void_p), ("maps", C.c_void_p), ("scene_map", C.c_void_p),
+                ("map_from_world", C.c_void_p), ("sim_dt", C.c_double), ("stat_dt", C.c_double),
+                ("num_scenes", C.c_int32), ("B_all", C.c_int32), ("n_sem", C.c_int32), ("height", C.c_int32), ("width", C.c_int32),
+                ("num_maps", C.c_int32), ("map_h", C.c_int32), ("map_w", C.c_int32), ("drivable_layer", C.c_int32),
+                ("px_per_m", C.c_float), ("ego_center", C.c_float * 2), ("no_map_fill", C.c_float)]
+
+
+METRICS_AGENT_COLS = ("steps", "steps_valid", "off_road_sum", "off_road_disk_sum", "coll_any", "coll_front", "coll_rear", "coll_side",
+                      "coll_disk", "failure_offroad", "failure_collision", "failure_any", "speed", "lon_acc", "lat_acc", "jerk")
+METRICS_SCENE_COLS = 16      # include/cld.h CLD_METRICS_SCENE_COLS
+
 GOAL_KINDS = {"global_target_pos": 1, "global_target_pos_at_time": 2}      # cld_goal.kind (0 = off)
 
 _P = C.c_void_p
@@ -145,6 +158,9 @@ SIGNATURES = {
     "cld_set_goal_term": (C.c_int, [_P, C.POINTER(CldGoal)]),
     "cld_world_step": (C.c_int, [_P, _P, _P, _P, C.c_int32, _P, _P, C.c_int32, _P]),
     "cld_rasterize": (C.c_int, [_P, C.POINTER(CldRaster), C.c_int32, C.c_int32, _P, _P, _P, _P]),
+    "cld_scene_metrics_state_bytes": (C.c_size_t, [C.c_int32]),
+    "cld_scene_metrics_step": (C.c_int, [_P, C.POINTER(CldSceneMetrics), _P, _P, _P, _P, C.c_int32, _P]),
+    "cld_scene_metrics_read": (C.c_int, [_P, C.POINTER(CldSceneMetrics), _P, _P, _P, _P]),
     "cld_profile_enable": (C.c_int, [_P, C.c_int32]),
     "cld_profile_read": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
     "cld_profile_read_executed": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32)]),

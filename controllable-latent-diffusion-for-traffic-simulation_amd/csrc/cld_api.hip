@@ -2055,6 +2055,62 @@ int cld_rasterize(cld_handle h, const cld_raster* r, int32_t row0, int32_t B, fl
     return CLD_OK;
 }
 
+/* ---- closed-loop episode metrics (metrics_kernels.hip) ---- */
+static_assert(CLD_METRICS_AGENT_COLS == METRICS_AGENT_COLS && CLD_METRICS_SCENE_COLS == METRICS_SCENE_COLS, "include/cld.h");
+
+size_t cld_scene_metrics_state_bytes(int32_t B_all) { return B_all < 1 ? 0 : (size_t)B_all * METRICS_ROW_BYTES; }
+
+static int check_scene_metrics(cld_handle h, const char* fn, const cld_scene_metrics* m, const void* state, MetricsArgs* a) {
+    const std::string f(fn);
+    if (!m || !state || !m->extent || !m->scene_start) return fail(h, CLD_ERR_ARG, f + ": null argument");
+    if (reinterpret_cast<uintptr_t>(state) % 16) return fail(h, CLD_ERR_ARG, f + ": state must be 16-byte aligned");
+    if (m->num_scenes < 1 || m->B_all < 1 || m->B_all > CLD_RASTER_MAX_AGENTS || m->num_scenes > m->B_all)
+        return fail(h, CLD_ERR_ARG, f + ": num_scenes / B_all out of range (1 <= num_scenes <= B_all <= CLD_RASTER_MAX_AGENTS)");
+    if (m->height < 1 || m->width < 1 || (int64_t)m->height * m->width > CLD_RASTER_MAX_PIXELS)
+        return fail(h, CLD_ERR_ARG, f + ": height x width out of range (include/cld.h CLD_RASTER_MAX_PIXELS)");
+    if (!(m->px_per_m > 0.f)) return fail(h, CLD_ERR_ARG, f + ": px_per_m must be positive");
+    if (m->n_sem < 1 || m->n_sem > CLD_RASTER_MAX_PLANES || m->drivable_layer < 0 || m->drivable_layer >= m->n_sem)
+        return fail(h, CLD_ERR_ARG, f + ": drivable_layer must be one of the n_sem >= 1 layers");
+    if (m->maps && (!m->scene_map || !m->map_from_world || m->num_maps < 1 || m->map_h < 1 || m->map_w < 1 ||
+                    (int64_t)m->map_h * m->map_w > INT32_MAX))
+        return fail(h, CLD_ERR_ARG, f + ": maps need scene_map, map_from_world, num_maps, map_h and map_w");
+    if (!(m->sim_dt > 0.0) || !(m->stat_dt >= m->sim_dt) || !(m->stat_dt / m->sim_dt < 1e6))
+        return fail(h, CLD_ERR_ARG, f + ": comfort needs 0 < sim_dt <= stat_dt");
+    *a = MetricsArgs{};
+    a->extent = m->extent; a->scene_start = m->scene_start; a->maps = m->maps; a->scene_map = m->scene_map;
+    a->map_from_world = m->map_from_world; a->state = const_cast<void*>(state);
+    a->num_scenes = m->num_scenes; a->B_all = m->B_all; a->n_sem = m->n_sem; a->num_maps = m->num_maps; a->map_h = m->map_h;
+    a->map_w = m->map_w; a->H = m->height; a->W = m->width; a->layer = m->drivable_layer;
+    a->ratio = (int)std::ceil(m->stat_dt / m->sim_dt);            // Comfort.get_episode_metrics: int(math.ceil(stat_dt / sim_dt))
+    a->ppm = m->px_per_m; a->ox = (1.f + m->ego_center[0]) * 0.5f * (float)m->width; a->oy = (1.f + m->ego_center[1]) * 0.5f * (float)m->height;
+    a->fill = m->no_map_fill; a->dt = (float)m->stat_dt;
+    return CLD_OK;
+}
+
+int cld_scene_metrics_step(cld_handle h, const cld_scene_metrics* m, const float* world, void* state, uint8_t* flags, int32_t* partner,
+                           int32_t step, void* stream) {
+    if (!h) return CLD_ERR_ARG;
+    if (!world) return fail(h, CLD_ERR_ARG, "cld_scene_metrics_step: null argument (world)");
+    if (step < 0) return fail(h, CLD_ERR_ARG, "cld_scene_metrics_step: step < 0");
+    MetricsArgs a;
+    int rc = check_scene_metrics(h, "cld_scene_metrics_step", m, state, &a);
+    if (rc) return rc;
+    a.world = world; a.flags = flags; a.partner = partner; a.step = step;
+    HIPCK(h, launch_scene_metrics_step(a, static_cast<hipStream_t>(stream)));
+    return CLD_OK;
+}
+
+int cld_scene_metrics_read(cld_handle h, const cld_scene_metrics* m, const void* state, float* per_agent, float* per_scene, void* stream) {
+    if (!h) return CLD_ERR_ARG;
+    if (!per_agent && !per_scene) return fail(h, CLD_ERR_ARG, "cld_scene_metrics_read: no output");
+    MetricsArgs a;
+    int rc = check_scene_metrics(h, "cld_scene_metrics_read", m, state, &a);
+    if (rc) return rc;
+    a.per_agent = per_agent; a.per_scene = per_scene;
+    HIPCK(h, launch_scene_metrics_read(a, static_cast<hipStream_t>(stream)));
+    return CLD_OK;
+}
+
 /* ---- training: what the U-Net and the LSTM-VAE entry points share ---- */
 static int param_info(cld_handle h, const char* fn, const TrainParam* table, int count, int32_t i, const char** name, size_t* offset,
                       size_t* numel, int32_t* shape, int32_t* ndim) {

@@ -282,6 +282,27 @@ struct RasterArgs {
 size_t raster_lds_bytes(int H, int W);
 hipError_t launch_raster(const RasterArgs& a, hipStream_t s);
 
+// the closed-loop episode metrics (metrics_kernels.hip; src/tbsim/envs/env_metrics.py:147-311, 391-646, 1436-1501): one step launch per
+// environment step over all agents of all scenes updates one accumulator row per agent; the read launch finalises the rows
+constexpr int METRICS_ROW_BYTES = 128, METRICS_AGENT_COLS = 16, METRICS_SCENE_COLS = 16;
+struct MetricsArgs {
+    const float* world;               // [B_all, 3] world x, y, yaw at this step (step launch)
+    const float* extent;              // [B_all, 3]
+    const int* scene_start;           // [num_scenes + 1]
+    const float* maps;                // [num_maps, n_sem, map_h, map_w] or null
+    const int* scene_map;             // [num_scenes], < 0: no map (read only when maps != null)
+    const float* map_from_world;      // [num_maps, 3, 3]
+    void* state;                      // [B_all] rows of METRICS_ROW_BYTES
+    unsigned char* flags;             // [B_all, 4] or null (step launch)
+    int* partner;                     // [B_all] or null (step launch)
+    float* per_agent;                 // [B_all, METRICS_AGENT_COLS] or null (read launch)
+    float* per_scene;                 // [num_scenes, METRICS_SCENE_COLS] or null (read launch)
+    int num_scenes, B_all, n_sem, num_maps, map_h, map_w, H, W, layer, step, ratio;
+    float ppm, ox, oy, fill, dt;
+};
+hipError_t launch_scene_metrics_step(const MetricsArgs& a, hipStream_t s);
+hipError_t launch_scene_metrics_read(const MetricsArgs& a, hipStream_t s);
+
 // ---- ContextEncoder (models/context_utils.py:8-61; context_kernels.hip) ------------------------------------
 // stem: image [B,34,224,224] NCHW -> y [B,112,112,64] NHWC = ReLU(BN(conv 7x7/2)); wq: packed by pack_stem_weights
 // pooled != null: MaxPool2d(3, 2, 1) fused (y unused): pooled [B,56,56,64] NHWC, zero-filled by the launcher, completed by atomic max

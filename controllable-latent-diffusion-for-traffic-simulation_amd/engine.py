@@ -1000,6 +1000,77 @@ class Engine:
                         "cld_rasterize")
         return image, drv, rfw
 
+    # ------------------------------------------------------------------ closed-loop episode metrics
+    def scene_metrics_setup(self, scene_start, extent, maps=None, scene_map=None, map_from_world=None, drivable_layer: int = 0,
+                            sim_dt: float = 0.1, stat_dt: float = 0.5, height: int = 224, width: int = 224, px_per_m: float = 2.0,
+                            ego_center=(-0.5, 0.0), no_map_fill: float = -1.0, n_sem: int = 3):
+        """The `cld_scene_metrics` struct of a scene set (include/cld.h) -> (struct, B_all, num_scenes, the tensors it points to).
+        scene_start is checked here to split the agents into scenes -- the library cannot read it without a synchronisation and never
+        validates its contents; an int32 tensor already on the device is copied to the host once for the check -- everything else is
+        checked by the library."""
+        ext = self._f32(extent)
+        if ext.dim() != 2 or ext.shape[1] != 3:
+            raise CldError(f"scene metrics: extent must be [B_all,3], got {tuple(ext.shape)}")
+        B_all = int(ext.shape[0])
+        host = torch.as_tensor(scene_start).to(torch.int64).reshape(-1).cpu()
+        if host.numel() < 2 or int(host[0]) != 0 or int(host[-1]) != B_all or bool((host[1:] <= host[:-1]).any()):
+            raise CldError(f"scene metrics: scene_start {host.tolist()} does not split the {B_all} agents into scenes")
+        ss = host.to(self.device, torch.int32).contiguous()
+        S = int(ss.numel()) - 1
+        mp = sm = mfw = None
+        num_maps = map_h = map_w = 0
+        if maps is not None:
+            mp = self._f32(maps)
+            if mp.dim() != 4 or mp.shape[1] != n_sem:
+                raise CldError(f"scene metrics: maps must be [num_maps,{n_sem},map_h,map_w], got {tuple(mp.shape)}")
+            num_maps, map_h, map_w = int(mp.shape[0]), int(mp.shape[2]), int(mp.shape[3])
+            if scene_map is None or map_from_world is None:
+                raise CldError("scene metrics: maps need scene_map and map_from_world")
+            sm = torch.as_tensor(scene_map).to(self.device, torch.int32).contiguous()
+            if tuple(sm.shape) != (S,):
+                raise CldError(f"scene metrics: scene_map must be [{S}], got {tuple(sm.shape)}")
+            mfw = self._f32(map_from_world, (num_maps, 3, 3))
+        dp = lambda t: None if t is None else t.data_ptr()
+        st = _lib.CldSceneMetrics(ext.data_ptr(), ss.data_ptr(), dp(mp), dp(sm), dp(mfw), float(sim_dt), float(stat_dt), S, B_all,
+                                  int(n_sem), int(height), int(width), num_maps, map_h, map_w, int(drivable_layer), float(px_per_m),
+                                  (C.c_float * 2)(float(ego_center[0]), float(ego_center[1])), float(no_map_fill))
+        return st, B_all, S, (ext, ss, mp, sm, mfw)
+
+    def scene_metrics_state(self, B_all: int):
+        """An empty accumulator buffer for B_all agents (cld_scene_metrics_state_bytes; all-zero = empty)."""
+        return torch.zeros(int(self.lib.cld_scene_metrics_state_bytes(int(B_all))), dtype=torch.uint8, device=self.device)
+
+    def _metrics_state(self, setup, state):
+        need = int(self.lib.cld_scene_metrics_state_bytes(setup[1]))
+        if not (isinstance(state, torch.Tensor) and state.device == self.device and state.dtype == torch.uint8 and state.is_contiguous()
+                and state.numel() == need):
+            raise CldError(f"scene metrics: state must be a contiguous uint8 tensor of {need} bytes on {self.device} (scene_metrics_state)")
+        return state
+
+    def scene_metrics_step(self, setup, world, state, step: int, want_flags: bool = False):
+        """One environment step of the episode metrics (cld_scene_metrics_step): world [B_all,3] -> `state` updated in place; with
+        want_flags -> (flags [B_all,4] uint8, partner [B_all] int32).  No host synchronisation."""
+        st, B_all = setup[0], setup[1]
+        state = self._metrics_state(setup, state)
+        world = self._f32(world, (B_all, 3))
+        flags = torch.empty(B_all, 4, dtype=torch.uint8, device=self.device) if want_flags else None
+        partner = torch.empty(B_all, dtype=torch.int32, device=self.device) if want_flags else None
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cld_scene_metrics_step(self._h, C.byref(st), _ptr(world), _ptr(state), _ptr(flags), _ptr(partner),
+                                                        int(step), self._stream()), "cld_scene_metrics_step")
+        return (flags, partner) if want_flags else None
+
+    def scene_metrics_read(self, setup, state):
+        """cld_scene_metrics_read -> (per_agent [B_all,16], per_scene [num_scenes,16]); columns: include/cld.h."""
+        st, B_all, S = setup[0], setup[1], setup[2]
+        state = self._metrics_state(setup, state)
+        per_agent = torch.empty(B_all, len(_lib.METRICS_AGENT_COLS), dtype=torch.float32, device=self.device)
+        per_scene = torch.empty(S, _lib.METRICS_SCENE_COLS, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cld_scene_metrics_read(self._h, C.byref(st), _ptr(state), _ptr(per_agent), _ptr(per_scene),
+                                                        self._stream()), "cld_scene_metrics_read")
+        return per_agent, per_scene
+
     # ------------------------------------------------------------------ measurement
     def profile_enable(self, on: bool = True):
         self._check(self.lib.cld_profile_enable(self._h, int(on)), "cld_profile_enable")

@@ -21,6 +21,7 @@ from typing import Callable, Mapping, Optional
 import numpy as np
 import torch
 
+from ._lib import CldError
 from .dm_model import DmModel, repeat_guidance
 from .vae_model import VaeModel
 
@@ -335,7 +336,7 @@ class CldPolicy:
 
 
 def closed_loop_rollout(policy: CldPolicy, cond_fn: Callable, centroid, yaw, curr_states, n_sim_steps: int,
-                        n_step_action: int = 5, gather: Optional[Callable] = None, timers=None, **get_action_kwargs):
+                        n_step_action: int = 5, gather: Optional[Callable] = None, timers=None, metrics=None, **get_action_kwargs):
     """The loop of `rollout_episodes` (`src/tbsim/utils/env_utils.py:255-304`) kept on the device:
     obs -> get_action -> take `n_step_action` steps of the plan -> new world pose -> re-plan.
     `cond_fn(step, world [B,3], curr_states [B,4], plans) -> cond_feat [B,256]` stands in for the observation +
@@ -346,6 +347,9 @@ def closed_loop_rollout(policy: CldPolicy, cond_fn: Callable, centroid, yaw, cur
     `parallel.gather_trajectories`) runs once per sim step; `timers` (`cld_amd.timer.Timers`) collects the per-phase
     times under the reference's keys "obs" / "network" / "env_step" / "step" (env_utils.py:268-298).
     The world moves on the EXECUTED trajectory (the selected sample, stationary agents held in place).
+    `metrics` (`cld_amd.metrics.RolloutMetrics`): after the environment step of each sim step the `n_step_action` executed states of every
+    agent are scored on the device (`metrics.add_plans` on what `gather` returned, or on this rank's trajectories without `gather`;
+    that tensor must cover the B_all agents of `metrics`); without it the loop is exactly what it was.
     With a goal loss configured (`global_target_pos`, `global_target_pos_at_time`) the observation must tell get_action where the
     agents are and where they have been; the fields `cond_fn`'s observation lacks are filled in here: `world_from_agent` /
     `agent_from_world` [B,3,3] from the current world pose, and `agent_hist` [B,n_step_action,2]: the `n_step_action` executed states
@@ -392,6 +396,12 @@ def closed_loop_rollout(policy: CldPolicy, cond_fn: Callable, centroid, yaw, cur
                 if has_goal:
                     hist_world = transform_points(traj[:, :n_step_action, :2], frames_from_pose(world))
                 world, cs = eng.world_step(traj, world[:, :2].contiguous(), world[:, 2].contiguous(), n_step_action - 1)
+                if metrics is not None:
+                    scored = plans if gather is not None else traj
+                    if tuple(scored.shape) != (metrics.B_all, 52, 6):
+                        raise CldError(f"closed_loop_rollout: metrics= scores all {metrics.B_all} agents, the executed plans are "
+                                       f"{tuple(scored.shape)} (pass gather= so that every rank's plans are there)")
+                    metrics.add_plans(scored)
         poses.append(world)
     return torch.stack(poses)
 

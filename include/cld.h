@@ -493,6 +493,71 @@ int cld_rasterize(cld_handle h, const cld_raster* r, int32_t row0, int32_t B,
                   float* image /*[B, T_hist+n_sem, H, W]*/, uint8_t* drivable /*[B,H,W] or NULL*/,
                   float* raster_from_world /*[B,3,3] or NULL*/, void* stream);
 
+/* The episode metrics of a closed-loop rollout, kept on the device: what upstream registers for evaluation
+ * (src/tbsim/evaluation/env_builders.py:37-50) as OffRoadRate, DiskOffRoadRate, CollisionRate, DiskCollisionRate, CriticalFailure and
+ * Comfort (src/tbsim/envs/env_metrics.py:147-239, 241-311, 391-487, 489-580, 582-646, 1436-1501).  Needs no weights.
+ * cld_scene_metrics_step is one environment step over all B_all agents of all scenes: world [B_all,3] (x, y, h) -> one accumulator row per
+ * agent in `state` (cld_scene_metrics_state_bytes(B_all) bytes, 16-byte aligned, all-zero = empty, updated in place; opaque).
+ * Agent i is VALID at a step when neither x nor y is NaN.  With ox, oy the raster offsets of cld_rasterize and drv(i; u, v) the byte
+ * cld_rasterize writes to drivable[i, v, u] for an agent standing at this step's pose (agent point ((u - ox) / ppm, (v - oy) / ppm), rotated
+ * by h, shifted to the world, map pixel rint(map_from_world . p) of layer `drivable_layer`, value != 0; fill and "no map" are drivable):
+ *   off_road       (OffRoadRate.compute_per_step with use_center, tbsim/utils/metrics.py:451-481) valid: 1 - drv at the centroid's raster
+ *                  pixel = (ox, oy) rounded half to even, then clamped to the raster; invalid: not counted (flags byte 255).
+ *   off_road_disk  (DiskOffRoadRate, metrics.py:507-547) r = px_per_m min(e0, e1) / 2 (get_raster_pix2m() is px_per_m); 52 samples
+ *                  (ox, oy) + (r k / 4) (cos a, sin a), k = 1 .. 4 (major), a = the 13 points of linspace(0, 2 pi, 13), both ends kept as
+ *                  upstream does, (cos, sin) a constant table formed in double; each sample is clamped to the raster, rounded, clamped
+ *                  again; 1 if any sample is not drivable.  Invalid: not counted (255).
+ *   coll_disk      (DiskCollisionRate.compute_per_step) some valid j != i of i's scene has |p_i - p_j| < min(e_i) / 2 + min(e_j) / 2.
+ *   coll_box, type (CollisionRate.compute_per_step -> geometry_utils.detect_collision:339-401) boxes with corners p +- (e0 / 2)(cos h, sin h)
+ *                  +- (e1 / 2)(-sin h, cos h); the partner is the lowest-index valid j != i of the scene whose box overlaps i's
+ *                  (separating-axis test on the four edge normals, touching counts); the type is the argmax (first wins) over the lengths
+ *                  of i's front (+e0 / 2), rear, left (+e1 / 2) and right sides inside the partner's box (each segment clipped against the four
+ *                  half-planes), remapped by min(index, 2): FRONT, REAR, SIDE.  PARITY UNPINNED: upstream decides both with shapely, which
+ *                  is not available where the goldens are recorded; the two are held to a float64 restatement of this definition.
+ *                  An invalid agent records 0 for the three collision quantities, as upstream does.
+ *   comfort        (Comfort) R = ceil(stat_dt / sim_dt); on steps with step % R == 0 the pose joins a three-deep ring.  With dt = stat_dt:
+ *                  vel = dpos / dt, speed = |vel|, acc = |dvel| / dt, lon = |acc cos h|, lat = |acc sin h| with the yaw of the FIRST of the
+ *                  three positions (as upstream indexes it), jerk = |dacc| / dt.  Running sums (fp64) and counts; NaN terms are not counted.
+ * flags [B_all,4] (optional): off_road, off_road_disk, coll_disk, box code 0 none / 1 FRONT / 2 REAR / 3 SIDE; partner [B_all] (optional):
+ * the box partner's index, -1: none.  A scene may hold any number of agents (the partner loop strides over it).
+ * cld_scene_metrics_read finalises the rows (either output may be NULL):
+ *   per_agent [B_all, CLD_METRICS_AGENT_COLS]: steps seen, steps valid, off_road sum, off_road_disk sum, max over time of coll_any, FRONT,
+ *     REAR, SIDE, coll_disk, any over time of off_road / of coll_any / of either, nanmean of speed, lon_acc, lat_acc, jerk (NaN: no term).
+ *   per_scene [num_scenes, CLD_METRICS_SCENE_COLS], the values of get_episode_metrics:
+ *     0, 1  OffRoadRate rate = flags summed over valid records / valid records (NaN for a scene without one), nframe = mean over the
+ *           scene's agents of the per-agent sum (an agent without a valid record counts with 0, as pandas' sum does);
+ *     2, 3  DiskOffRoadRate rate, nframe;  4 .. 7 CollisionRate FRONT, REAR, SIDE, coll_any: means over the scene's agents of the max over time;
+ *     8     DiskCollisionRate coll_any;
+ *     9 .. 11 CriticalFailure failure_offroad, failure_collision, failure_any: the share of the scene's agents that were off road / in a box
+ *           collision / either at ANY step -- upstream's class discards its num_collision_frames / num_offroad_frames arguments
+ *           (env_metrics.py:584-587), so one frame is a failure; NaN off_road records are skipped by pandas' any();
+ *     12 .. 15 Comfort speed, lon_acc, lat_acc, jerk: nanmean over the scene's agents of the per-agent nanmean (NaN: no agent has a term).
+ * CLD_ERR_ARG (nothing is skipped silently): NULL world / state / extent / scene_start, B_all or num_scenes < 1, height * width beyond
+ * CLD_RASTER_MAX_PIXELS, px_per_m <= 0, maps without their companions, drivable_layer outside [0, n_sem), sim_dt <= 0 or stat_dt < sim_dt
+ * (upstream's assert), step < 0.  The CONTENTS of scene_start are never validated by the library: it is device memory, and reading it
+ * would need a synchronisation.  The caller guarantees 0 = scene_start[0] < ... < scene_start[num_scenes] = B_all (the Python layer checks
+ * it on the host); the kernels clamp what they read from it, so a malformed split cannot make them read or write out of bounds, but
+ * its metrics are then meaningless. */
+#define CLD_METRICS_AGENT_COLS 16
+#define CLD_METRICS_SCENE_COLS 16
+typedef struct cld_scene_metrics {
+    const float*   extent;          /* DEVICE [B_all, 3] length (along the heading), width, height: the layout of cld_collision */
+    const int32_t* scene_start;     /* DEVICE [num_scenes + 1] */
+    const float*   maps;            /* DEVICE [num_maps, n_sem, map_h, map_w] or NULL */
+    const int32_t* scene_map;       /* DEVICE [num_scenes], < 0: no map */
+    const float*   map_from_world;  /* DEVICE [num_maps, 3, 3] */
+    double  sim_dt, stat_dt;
+    int32_t num_scenes, B_all, n_sem, height, width, num_maps, map_h, map_w, drivable_layer;
+    float   px_per_m, ego_center[2], no_map_fill;
+} cld_scene_metrics;
+
+size_t cld_scene_metrics_state_bytes(int32_t B_all);
+int cld_scene_metrics_step(cld_handle h, const cld_scene_metrics* m, const float* world, void* state,
+                           uint8_t* flags /*[B_all,4] or NULL*/, int32_t* partner /*[B_all] or NULL*/, int32_t step, void* stream);
+int cld_scene_metrics_read(cld_handle h, const cld_scene_metrics* m, const void* state,
+                           float* per_agent /*[B_all, CLD_METRICS_AGENT_COLS] or NULL*/,
+                           float* per_scene /*[num_scenes, CLD_METRICS_SCENE_COLS] or NULL*/, void* stream);
+
 /* Which form a Conv1d(k5) + GroupNorm + Mish launch takes (no handle, no device call; tests): CLD_FORM_WINOGRAD or CLD_FORM_DIRECT for a
  * layer with `c1` (+ `c2` concatenated) input channels, `c_out` output channels and `l_in` rows per agent in a launch set of `rows` agents
  * (padded to 16 inside), with `forced_form` = what cld_debug_force_kernel(CLD_KERNEL_CONV5, ...) would hold (CLD_FORM_AUTO: by size).
