@@ -87,6 +87,13 @@ class CldMapCollision(C.Structure):
                 ("num_points_l", C.c_int32), ("num_points_w", C.c_int32), ("decay_rate", C.c_float), ("moving_speed_th", C.c_float)]
 
 
+class CldMapSource(C.Structure):
+    """include/cld.h `cld_map_source` (the scene maps a map_collision term without a drivable_map reads, device pointers)."""
+    _fields_ = [("maps", C.c_void_p), ("scene_map", C.c_void_p), ("map_from_world", C.c_void_p), ("world", C.c_void_p),
+                ("num_scenes", C.c_int32), ("num_maps", C.c_int32), ("n_sem", C.c_int32), ("map_h", C.c_int32), ("map_w", C.c_int32),
+                ("drivable_layer", C.c_int32), ("px_per_m", C.c_float), ("ego_center", C.c_float * 2), ("no_map_fill", C.c_float)]
+
+
 class CldGoal(C.Structure):
     """include/cld.h `cld_goal` (upstream's GlobalTargetPosLoss / GlobalTargetPosAtTimeLoss per agent, device pointers)."""
     _fields_ = [("target_pos", C.c_void_p), ("agent_from_world", C.c_void_p), ("kind", C.c_void_p), ("target_time", C.c_void_p),
@@ -156,6 +163,7 @@ SIGNATURES = {
     "cld_map_collision_loss": (C.c_int, [_P, _P, C.POINTER(CldMapCollision), _P, _P, _P, C.c_int32, _P]),
     "cld_goal_loss": (C.c_int, [_P, _P, C.POINTER(CldGoal), _P, _P, _P, C.c_int32, _P]),
     "cld_set_goal_term": (C.c_int, [_P, C.POINTER(CldGoal)]),
+    "cld_set_map_source": (C.c_int, [_P, C.POINTER(CldMapSource)]),
     "cld_world_step": (C.c_int, [_P, _P, _P, _P, C.c_int32, _P, _P, C.c_int32, _P]),
     "cld_rasterize": (C.c_int, [_P, C.POINTER(CldRaster), C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "cld_scene_metrics_state_bytes": (C.c_size_t, [C.c_int32]),

@@ -54,6 +54,8 @@ struct cld_handle_s {
     bool finalized = false, has_decoder = false, has_unet = false;
     cld_goal goal{};                                 // cld_set_goal_term: the goal term every guided call adds while has_goal
     bool has_goal = false;
+    cld_map_source map_source{};                     // cld_set_map_source: what a cld_map_collision without a drivable_map reads while has_map_source
+    bool has_map_source = false;
     std::vector<void*> dev_allocs;
     // schedule (host, fp32 as in dm_model.py:29-56)
     std::vector<float> x_t_cof, noise_cof, plvc, sqrt_acp, sqrt_1m_acp, sqrt_recip_acp, sqrt_recipm1_acp;
@@ -1462,16 +1464,28 @@ static int check_collision(cld_handle h, const char* fn, const cld_collision* c,
 }
 
 static int check_map_collision(cld_handle h, const char* fn, const cld_map_collision* c, int B) {
-    if (!c->extent || !c->raster_from_agent || !c->drivable_map || !c->curr_speed || !c->scene_start)
+    if (!c->extent || !c->raster_from_agent || !c->curr_speed || !c->scene_start)
         return fail(h, CLD_ERR_ARG, std::string(fn) + ": map collision term: null pointer");
+    if (!c->drivable_map && !h->has_map_source)
+        return fail(h, CLD_ERR_ARG, std::string(fn) + ": map collision term: drivable_map is NULL and no map source is set (cld_set_map_source)");
+    if (!c->drivable_map && h->map_source.num_scenes != c->num_scenes)
+        return fail(h, CLD_ERR_ARG, std::string(fn) + ": map collision term: the map source holds " + std::to_string(h->map_source.num_scenes) +
+                                        " scenes, the term " + std::to_string(c->num_scenes));
     if (c->num_scenes < 1 || c->num_samp < 1 || B % c->num_samp || c->H < 1 || c->W < 1)
         return fail(h, CLD_ERR_ARG, std::string(fn) + ": map collision term: B must be agents x num_samp, a map of H x W >= 1");
     if (c->num_points_l < 1 || c->num_points_w < 1 || c->num_points_l * c->num_points_w > 256)
         return fail(h, CLD_ERR_ARG, std::string(fn) + ": map collision term: 1..256 sample points per box");
     return CLD_OK;
 }
-static MapCollisionArgs map_args(const cld_map_collision* c, const float* traj, const float* grad_in, float* loss, float* grad) {
+static MapCollisionArgs map_args(cld_handle h, const cld_map_collision* c, const float* traj, const float* grad_in, float* loss, float* grad) {
     MapCollisionArgs a{};
+    if (!c->drivable_map && h->has_map_source) {     // map mode; with a drivable_map the source is ignored
+        const cld_map_source& m = h->map_source;
+        a.maps = m.maps; a.scene_map = m.scene_map; a.map_from_world = m.map_from_world; a.world = m.world;
+        a.num_maps = m.num_maps; a.n_sem = m.n_sem; a.map_h = m.map_h; a.map_w = m.map_w; a.layer = m.drivable_layer;
+        a.ppm = m.px_per_m; a.ox = (1.f + m.ego_center[0]) * 0.5f * (float)c->W; a.oy = (1.f + m.ego_center[1]) * 0.5f * (float)c->H;      // cld_rasterize's offsets
+        a.fill = m.no_map_fill;
+    }
     a.traj = traj; a.extent = c->extent; a.raster_from_agent = c->raster_from_agent; a.drivable_map = c->drivable_map;
     a.curr_speed = c->curr_speed; a.scene_start = c->scene_start; a.scene_weight = c->scene_weight; a.grad_in = grad_in;
     a.loss = loss; a.grad = grad; a.num_scenes = c->num_scenes; a.num_samp = c->num_samp; a.H = c->H; a.W = c->W;
@@ -1572,7 +1586,7 @@ static int run_guidance(cld_handle h, const Ws& w, const cld_guidance* gd, int B
             g.ext_grad = w.col_grad;
         }
         if (gd->map_collision) {                     // adds to whatever gradient is there already (caller's ext_grad, agent collisions)
-            HIPCK(h, launch_map_collision(map_args(gd->map_collision, w.col_traj, gd->collision ? w.col_grad : gd->ext_grad, nullptr, w.col_grad), B, s));
+            HIPCK(h, launch_map_collision(map_args(h, gd->map_collision, w.col_traj, gd->collision ? w.col_grad : gd->ext_grad, nullptr, w.col_grad), B, s));
             g.ext_grad = w.col_grad;
         }
         if (h->has_goal) {                           // likewise: on top of the caller's ext_grad and the collision gradients
@@ -1999,7 +2013,7 @@ int cld_map_collision_loss(cld_handle h, const float* traj, const cld_map_collis
     if (!traj || !c || B < 1 || (!loss && !grad)) return fail(h, CLD_ERR_ARG, "cld_map_collision_loss: bad argument");
     int rc = check_map_collision(h, "cld_map_collision_loss", c, B);
     if (rc) return rc;
-    HIPCK(h, launch_map_collision(map_args(c, traj, grad_in, loss, grad), B, static_cast<hipStream_t>(stream)));
+    HIPCK(h, launch_map_collision(map_args(h, c, traj, grad_in, loss, grad), B, static_cast<hipStream_t>(stream)));
     return CLD_OK;
 }
 
@@ -2017,6 +2031,23 @@ int cld_set_goal_term(cld_handle h, const cld_goal* g) {
     if (!h) return CLD_ERR_ARG;
     h->has_goal = g != nullptr;
     h->goal = g ? *g : cld_goal{};
+    return CLD_OK;
+}
+
+int cld_set_map_source(cld_handle h, const cld_map_source* m) {
+    if (!h) return CLD_ERR_ARG;
+    if (m) {
+        if (!m->world) return fail(h, CLD_ERR_ARG, "cld_set_map_source: null argument (world)");
+        if (m->num_scenes < 1) return fail(h, CLD_ERR_ARG, "cld_set_map_source: num_scenes < 1");
+        if (!(m->px_per_m > 0.f)) return fail(h, CLD_ERR_ARG, "cld_set_map_source: px_per_m must be positive");
+        if (m->n_sem < 1 || m->n_sem > CLD_RASTER_MAX_PLANES || m->drivable_layer < 0 || m->drivable_layer >= m->n_sem)
+            return fail(h, CLD_ERR_ARG, "cld_set_map_source: drivable_layer must be one of the n_sem >= 1 layers");
+        if (m->maps && (!m->scene_map || !m->map_from_world || m->num_maps < 1 || m->map_h < 1 || m->map_w < 1 ||
+                        (int64_t)m->map_h * m->map_w > INT32_MAX))
+            return fail(h, CLD_ERR_ARG, "cld_set_map_source: maps need scene_map, map_from_world, num_maps, map_h and map_w");
+    }
+    h->has_map_source = m != nullptr;
+    h->map_source = m ? *m : cld_map_source{};
     return CLD_OK;
 }
 

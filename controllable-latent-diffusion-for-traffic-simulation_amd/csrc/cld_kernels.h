@@ -282,6 +282,35 @@ struct RasterArgs {
 size_t raster_lds_bytes(int H, int W);
 hipError_t launch_raster(const RasterArgs& a, hipStream_t s);
 
+// The value of raster pixel (u, v) of an agent standing at (xi, yi) with heading (c, s) = (cos h, sin h): include/cld.h's semantic plane,
+// the float behind drv(i; u, v).  raster_kernel writes it and map_collision_kernel's map mode reads it; the two must give the same
+// BITS, so every rounding is spelled out here and nothing is left to the compiler's contraction (which had chosen differently for the
+// two rows of the map matrix, and differently again in scene_metrics_step_kernel): products and sums round one by one except where
+// an fma is written.  The roundings are the ones raster_kernel has always had.
+struct MapView {
+    float xi, yi, c, s;               // the agent's world pose
+    float inv_ppm, ox, oy;            // metres per raster pixel (1.f / ppm, one IEEE division), the raster offsets
+    float m00, m01, m02, m10, m11, m12;      // map_from_world of the scene's map
+    float mw, mh;                     // (float)map_w, (float)map_h
+    const float* src;                 // the layer [map_h, map_w], or null: no map (every pixel takes `fill`)
+    int map_w;
+    float fill;
+};
+__device__ __forceinline__ float map_agent_coord(int px, float offset, float inv_ppm) {      // (u - ox) / ppm, (v - oy) / ppm
+#pragma clang fp contract(off)
+    return ((float)px - offset) * inv_ppm;
+}
+__device__ __forceinline__ float map_pixel_value(const MapView& f, float ax, float ay) {
+#pragma clang fp contract(off)
+    if (!f.src) return f.fill;
+    const float wx = f.xi + __builtin_fmaf(-f.s, ay, f.c * ax);
+    const float wy = f.yi + __builtin_fmaf(f.s, ax, f.c * ay);
+    const float mx = rintf((f.m00 * wx + f.m01 * wy) + f.m02);
+    const float my = rintf(__builtin_fmaf(f.m11, wy, f.m10 * wx) + f.m12);
+    if (mx >= 0.f && mx < f.mw && my >= 0.f && my < f.mh) return f.src[(size_t)my * f.map_w + (size_t)mx];
+    return f.fill;
+}
+
 // the closed-loop episode metrics (metrics_kernels.hip; src/tbsim/envs/env_metrics.py:147-311, 391-646, 1436-1501): one step launch per
 // environment step over all agents of all scenes updates one accumulator row per agent; the read launch finalises the rows
 constexpr int METRICS_ROW_BYTES = 128, METRICS_AGENT_COLS = 16, METRICS_SCENE_COLS = 16;
@@ -423,6 +452,14 @@ struct MapCollisionArgs {
     float* grad;                     // [rows, 52, 6] or null
     int num_scenes, num_samp, H, W, num_points_l, num_points_w;
     float decay_rate, moving_speed_th;
+    // map mode (drivable_map == null; include/cld.h cld_map_source): the off-road flag of raster pixel (ix, iy) is taken from the scene's
+    // map with map_pixel_value at the pose world[agent].  Appended: the raster instance of the kernel reads nothing of it.
+    const float* maps;               // [num_maps, n_sem, map_h, map_w] or null (every pixel takes `fill`)
+    const int* scene_map;            // [num_scenes], < 0: no map
+    const float* map_from_world;     // [num_maps, 3, 3]
+    const float* world;              // [B_agents, 3] (x, y, h)
+    int num_maps, n_sem, map_h, map_w, layer;
+    float ppm, ox, oy, fill;
 };
 hipError_t launch_map_collision(const MapCollisionArgs& a, int rows, hipStream_t s);
 

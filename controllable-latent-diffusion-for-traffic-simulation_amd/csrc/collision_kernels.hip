@@ -191,6 +191,8 @@ hipError_t launch_agent_collision(const CollisionArgs& a, hipStream_t s) {
 // Upstream takes the distances from torch.cdist (its matrix-multiply path at 100 points: ~1e-4 m of rounding at these
 // coordinates, which also enters its backward); here they are exact differences, so values agree to rounding and gradients to
 // the reference's own ~0.3 % noise.
+// Two instances: the off-road flag from a per-agent drivable raster (what the kernel always was), or -- map_collision_kernel<true>,
+// include/cld.h cld_set_map_source -- from the scene's semantic map with cld_rasterize's own arithmetic, where nobody rasterised.
 namespace {
 constexpr int kMaxPts = 256;
 
@@ -198,6 +200,20 @@ __device__ __forceinline__ float unit_linspace(int a, int n) {      // torch.lin
     if (n <= 1) return -0.5f;
     const float step = 1.0f / (float)(n - 1);
     return a < n / 2 ? -0.5f + step * (float)a : 0.5f - step * (float)(n - 1 - a);
+}
+// Map mode's sample point in the agent frame and its raster coordinate: the roundings the raster instance of the kernel compiles to,
+// written out.  Both instances must put a sample into the same pixel, and contraction left to the compiler does not promise that (it
+// fused R[1] * ay into the sum in one instance and not in the other).  The raster instance keeps its plain expressions, so that it
+// compiles to the instructions it always had (read from ROCm 7.2.0's hipcc, -O3, gfx950); should a toolchain ever
+// contract those differently, the bit-identity test of the two modes (tests/test_gpu_map_source.py) says so, and these lines follow.
+__device__ __forceinline__ void sample_point(float lx, float wy, float cy, float sy, float px, float py, float& ax, float& ay) {
+#pragma clang fp contract(off)
+    ax = __builtin_fmaf(cy, lx, -(sy * wy)) + px;         // lx cy - wy sy + px
+    ay = __builtin_fmaf(sy, lx, cy * wy) + py;            // lx sy + wy cy + py
+}
+__device__ __forceinline__ float raster_coord(float r0, float r1, float r2, float ax, float ay) {
+#pragma clang fp contract(off)
+    return (r0 * ax + r1 * ay) + r2;
 }
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -229,6 +245,33 @@ struct Nearest {
     }
 };
 
+// kFromMap: the off-road flag of a sample's raster pixel comes from the scene's semantic map (MapCollisionArgs::maps .. fill) instead of a
+// per-agent drivable raster: the byte cld_rasterize would have written for an agent standing at world[b], looked up where it is needed
+// (map_pixel_value, the function raster_kernel itself calls: the same bits).  Everything behind the flag is the one code.
+template <bool kFromMap>
+__device__ __forceinline__ int& plan_scene() {          // (map mode only: the raster instance has no such word in LDS)
+    __shared__ int s_scene;
+    return s_scene;
+}
+
+// per plan, wave-uniform: the pose, 1 / ppm, the map matrix and the layer's base pointer of agent b of scene sc
+__device__ __forceinline__ MapView plan_map_view(const MapCollisionArgs& p, int b, int sc) {
+    MapView f{};
+    int m = (p.maps && sc >= 0) ? p.scene_map[sc] : -1;
+    if (m >= p.num_maps) m = -1;
+    const float* me = p.world + (size_t)b * 3;
+    f.xi = me[0]; f.yi = me[1]; f.c = cosf(me[2]); f.s = sinf(me[2]);      // (cosf, sinf as raster_kernel calls them)
+    f.inv_ppm = 1.f / p.ppm; f.ox = p.ox; f.oy = p.oy; f.fill = p.fill;
+    f.mw = (float)p.map_w; f.mh = (float)p.map_h; f.map_w = p.map_w;
+    if (m >= 0) {
+        const float* M = p.map_from_world + (size_t)m * 9;
+        f.m00 = M[0]; f.m01 = M[1]; f.m02 = M[2]; f.m10 = M[3]; f.m11 = M[4]; f.m12 = M[5];
+        f.src = p.maps + ((size_t)m * p.n_sem + p.layer) * p.map_h * p.map_w;
+    }
+    return f;
+}
+
+template <bool kFromMap>
 __global__ __launch_bounds__(64 * kMapWaves) void map_collision_kernel(const MapCollisionArgs p) {
     // per wave: the step's ON-road samples and OFF-road samples (x, y in the agent frame), compacted -- the search of an
     // off-road sample walks on-road candidates only, and the off-road samples fill the lanes from 0
@@ -241,19 +284,23 @@ __global__ __launch_bounds__(64 * kMapWaves) void map_collision_kernel(const Map
     const int P = p.num_points_l * p.num_points_w;
     if (tid == 0) {                                     // the agent's scene: weight / (agents of the scene x samples)
         float c = 0.f;
+        int sc = -1;
         for (int s = 0; s < p.num_scenes; ++s)
             if (b >= p.scene_start[s] && b < p.scene_start[s + 1]) {
                 const float w = p.scene_weight ? p.scene_weight[s] : 1.0f;
                 c = w / ((float)(p.scene_start[s + 1] - p.scene_start[s]) * (float)p.num_samp);
+                sc = s;
             }
         s_coef = c;
+        if constexpr (kFromMap) plan_scene<kFromMap>() = sc;
     }
     __syncthreads();
     const bool moving = fabsf(p.curr_speed[b]) > p.moving_speed_th;
     const float len = p.extent[b * 3 + 0], wid = p.extent[b * 3 + 1];
     const float inv_diag = 1.0f / sqrtf(len * len + wid * wid);
     const float* R = p.raster_from_agent + (size_t)b * 9;
-    const unsigned char* dm = p.drivable_map + (size_t)b * p.H * p.W;
+    const unsigned char* dm = kFromMap ? nullptr : p.drivable_map + (size_t)b * p.H * p.W;
+    const MapView f = kFromMap ? plan_map_view(p, b, plan_scene<kFromMap>()) : MapView{};
     float wsum = 0.f, wp = 1.f;
     for (int t = 0; t < TT; ++t) { wsum += wp; wp *= p.decay_rate; }
     for (int t = wave; t < TT; t += kMapWaves) {
@@ -268,10 +315,17 @@ __global__ __launch_bounds__(64 * kMapWaves) void map_collision_kernel(const Map
             float ax = 0.f, ay = 0.f;
             if (valid) {
                 const float lx = unit_linspace(k / p.num_points_w, p.num_points_l) * len, wy = unit_linspace(k % p.num_points_w, p.num_points_w) * wid;
-                ax = lx * cy - wy * sy + px; ay = lx * sy + wy * cy + py;
-                int ix = (int)(R[0] * ax + R[1] * ay + R[2]), iy = (int)(R[3] * ax + R[4] * ay + R[5]);      // .long(): truncation toward zero
+                int ix, iy;
+                if constexpr (kFromMap) {
+                    sample_point(lx, wy, cy, sy, px, py, ax, ay);
+                    ix = (int)raster_coord(R[0], R[1], R[2], ax, ay); iy = (int)raster_coord(R[3], R[4], R[5], ax, ay);
+                } else {
+                    ax = lx * cy - wy * sy + px; ay = lx * sy + wy * cy + py;
+                    ix = (int)(R[0] * ax + R[1] * ay + R[2]); iy = (int)(R[3] * ax + R[4] * ay + R[5]);      // .long(): truncation toward zero
+                }
                 ix = min(max(ix, 0), p.W - 1); iy = min(max(iy, 0), p.H - 1);
-                off = dm[(size_t)iy * p.W + ix] == 0;
+                if constexpr (kFromMap) off = map_pixel_value(f, map_agent_coord(ix, f.ox, f.inv_ppm), map_agent_coord(iy, f.oy, f.inv_ppm)) == 0.f;
+                else off = dm[(size_t)iy * p.W + ix] == 0;
             }
             // compaction in sample order (the order the candidates are walked in decides nothing but rounding-level ties)
             const unsigned long long m_off = __ballot(valid && off), m_on = __ballot(valid && !off);
@@ -338,7 +392,9 @@ __global__ __launch_bounds__(64 * kMapWaves) void map_collision_kernel(const Map
 
 hipError_t launch_map_collision(const MapCollisionArgs& a, int rows, hipStream_t s) {
     if (a.num_points_l < 1 || a.num_points_w < 1 || a.num_points_l * a.num_points_w > kMaxPts || a.num_samp < 1 || rows < 1) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(map_collision_kernel, dim3(rows), dim3(64 * kMapWaves), 0, s, a);
+    if (a.drivable_map) hipLaunchKernelGGL(map_collision_kernel<false>, dim3(rows), dim3(64 * kMapWaves), 0, s, a);
+    else if (a.world) hipLaunchKernelGGL(map_collision_kernel<true>, dim3(rows), dim3(64 * kMapWaves), 0, s, a);
+    else return hipErrorInvalidValue;
     return hipGetLastError();
 }
 

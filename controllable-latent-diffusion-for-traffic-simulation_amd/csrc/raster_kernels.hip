@@ -88,31 +88,25 @@ __global__ __launch_bounds__(kThreads) void raster_kernel(const RasterArgs p) {
     const int layer = plane - p.T;
     int m = p.maps ? p.scene_map[sc] : -1;
     if (m >= p.num_maps) m = -1;
-    float m00 = 0.f, m01 = 0.f, m02 = 0.f, m10 = 0.f, m11 = 0.f, m12 = 0.f;
-    const float* src = nullptr;
+    MapView f{};                                                 // the per-pixel lookup itself: map_pixel_value (cld_kernels.h)
+    f.xi = xi; f.yi = yi; f.c = c; f.s = s; f.ox = p.ox; f.oy = p.oy; f.fill = p.fill;
+    f.inv_ppm = 1.f / p.ppm;                                     // (metres per pixel: one division per workgroup)
+    f.mw = (float)p.map_w; f.mh = (float)p.map_h; f.map_w = p.map_w;
     if (m >= 0) {
         const float* M = p.map_from_world + (size_t)m * 9;
-        m00 = M[0]; m01 = M[1]; m02 = M[2]; m10 = M[3]; m11 = M[4]; m12 = M[5];
-        src = p.maps + ((size_t)m * p.n_sem + layer) * p.map_h * p.map_w;
+        f.m00 = M[0]; f.m01 = M[1]; f.m02 = M[2]; f.m10 = M[3]; f.m11 = M[4]; f.m12 = M[5];
+        f.src = p.maps + ((size_t)m * p.n_sem + layer) * p.map_h * p.map_w;
     }
     unsigned char* drv = (p.drivable && layer == 0) ? p.drivable + (size_t)i * HW : nullptr;
-    const float mw = (float)p.map_w, mh = (float)p.map_h, inv_ppm = 1.f / p.ppm;       // (metres per pixel: one division per workgroup)
     for (int g = tid; g < groups; g += kThreads) {
         const int p0 = g << 2;
         int v = p0 / p.W, u = p0 - v * p.W;
         float val[4];
-        float ay = ((float)v - p.oy) * inv_ppm;
+        float ay = map_agent_coord(v, f.oy, f.inv_ppm);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            float x = p.fill;
-            if (m >= 0) {
-                const float ax = ((float)u - p.ox) * inv_ppm;
-                const float wx = xi + (c * ax - s * ay), wy = yi + (s * ax + c * ay);
-                const float mx = rintf(m00 * wx + m01 * wy + m02), my = rintf(m10 * wx + m11 * wy + m12);
-                if (mx >= 0.f && mx < mw && my >= 0.f && my < mh) x = src[(size_t)my * p.map_w + (size_t)mx];
-            }
-            val[k] = x;
-            if (++u == p.W) { u = 0; ++v; ay = ((float)v - p.oy) * inv_ppm; }
+            val[k] = map_pixel_value(f, map_agent_coord(u, f.ox, f.inv_ppm), ay);
+            if (++u == p.W) { u = 0; ++v; ay = map_agent_coord(v, f.oy, f.inv_ppm); }
         }
         if (p.vec) {
             *reinterpret_cast<float4*>(out + p0) = make_float4(val[0], val[1], val[2], val[3]);

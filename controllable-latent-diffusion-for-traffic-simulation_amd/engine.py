@@ -29,6 +29,22 @@ CONTEXT_LAYERS += [(1, 2, 56 >> (_li - 1), 32 << _li, 64 << _li) for _li in rang
 # span k's output is span k + 1's input, span 11's the noise prediction [52, 4]
 UNET_SPANS = [(52, 4), (26, 64), (26, 128), (26, 128), (13, 128), (13, 256), (13, 256), (13, 256), (13, 256), (13, 128), (13, 128), (26, 128)]
 
+# the raster settings of cld_rasterize (config.yaml:81-86, :96); observe.py re-exports them
+RASTER_DEFAULTS = dict(height=224, width=224, px_per_m=2.0, ego_center=(-0.5, 0.0), no_map_fill=-1.0, max_neighbor_dist=30.0, n_sem=3)
+# what a `map_source` takes besides its tensors: the same settings (max_neighbor_dist concerns the history planes only and is accepted so
+# that a SceneObserver's settings pass as they are) and its own drivable_layer
+MAP_SOURCE_DEFAULTS = dict(RASTER_DEFAULTS, drivable_layer=0)
+
+
+def raster_frames(settings: Mapping, A: int):
+    """raster_from_agent [A,3,3] of cld_rasterize for raster settings named as RASTER_DEFAULTS names them (include/cld.h):
+    [[ppm, 0, (1 + ego_center[0]) / 2 * width], [0, ppm, (1 + ego_center[1]) / 2 * height], [0, 0, 1]]."""
+    cfg = {k: settings.get(k, RASTER_DEFAULTS[k]) for k in ("height", "width", "px_per_m", "ego_center")}
+    H, W, ppm, ec = cfg["height"], cfg["width"], cfg["px_per_m"], cfg["ego_center"]
+    m = torch.tensor([[ppm, 0.0, (1.0 + ec[0]) / 2.0 * W], [0.0, ppm, (1.0 + ec[1]) / 2.0 * H], [0.0, 0.0, 1.0]], dtype=torch.float32)
+    return m.expand(A, 3, 3).contiguous()
+
+
 def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else C.c_void_p(t.data_ptr())
 
@@ -438,24 +454,90 @@ class Engine:
         """dict(extent [A,3], raster_from_agent [A,3,3], drivable_map [A,H,W] (non-zero = drivable), curr_speed [A], scene_index |
         scene_sizes (default: one scene), weight: scalar or per-scene sequence, num_samp = 1, num_points_lw = (10, 10),
         decay_rate = 0.9, guide_moving_speed_th = 0.5) -> (CldMapCollision, tensors kept alive): upstream's MapCollisionLoss
-        (src/tbsim/utils/guidance_loss.py:717-875)."""
+        (src/tbsim/utils/guidance_loss.py:717-875).  In place of `drivable_map`: map_source = dict(maps, scene_map, map_from_world,
+        world [A,3], drivable_layer = 0, height, width, px_per_m, ego_center, no_map_fill as RASTER_DEFAULTS names them) --
+        the term then reads the scene maps themselves (H, W = height, width) and the struct has no drivable_map; the source goes to
+        the handle around the library call (_map_source_term)."""
         N = int(c.get("num_samp", 1))
         if B % N:
             raise CldError(f"map_collision: {B} rows are not a multiple of num_samp = {N}")
         A = B // N
+        missing = [k for k in ("extent", "raster_from_agent", "curr_speed") if c.get(k) is None]
+        if missing:
+            raise CldError(f"map_collision: missing {missing}")
         ext = self._f32(c["extent"], (A, 3)); rfa = self._f32(c["raster_from_agent"], (A, 3, 3)); spd = self._f32(c["curr_speed"], (A,))
-        dm = torch.as_tensor(c["drivable_map"])
-        if dm.dim() != 3 or dm.shape[0] != A:
-            raise CldError(f"map_collision: drivable_map must be [{A},H,W], got {tuple(dm.shape)}")
-        if not (dm.dtype == torch.uint8 and dm.device == self.device):     # (a resident uint8 map is taken as it is: non-zero = drivable)
-            dm = (dm != 0).to(self.device, torch.uint8)
-        dm = dm.contiguous()
+        ms = c.get("map_source")
+        if ms is not None and c.get("drivable_map") is not None:
+            raise CldError("map_collision: drivable_map and map_source are two ways to say where the road is; pass one")
+        if ms is None and c.get("drivable_map") is None:
+            raise CldError("map_collision needs drivable_map or map_source")
+        dm = None
+        if ms is None:
+            dm = torch.as_tensor(c["drivable_map"])
+            if dm.dim() != 3 or dm.shape[0] != A:
+                raise CldError(f"map_collision: drivable_map must be [{A},H,W], got {tuple(dm.shape)}")
+            if not (dm.dtype == torch.uint8 and dm.device == self.device):     # (a resident uint8 map is taken as it is: non-zero = drivable)
+                dm = (dm != 0).to(self.device, torch.uint8)
+            dm = dm.contiguous()
+            H, W = int(dm.shape[1]), int(dm.shape[2])
+        else:
+            unknown = sorted(set(ms) - set(MAP_SOURCE_DEFAULTS) - {"maps", "scene_map", "map_from_world", "world"})
+            if unknown:
+                raise CldError(f"map_collision: unknown map_source entries {unknown}")
+            H, W = int(ms.get("height", MAP_SOURCE_DEFAULTS["height"])), int(ms.get("width", MAP_SOURCE_DEFAULTS["width"]))
         sizes, start, wts = self._scene_blocks(c, A, "map_collision")
         nl, nw = (int(v) for v in c.get("num_points_lw", (10, 10)))
-        cc = _lib.CldMapCollision(ext.data_ptr(), rfa.data_ptr(), dm.data_ptr(), spd.data_ptr(), start.data_ptr(), wts.data_ptr(),
-                                  len(sizes), N, int(dm.shape[1]), int(dm.shape[2]), nl, nw, float(c.get("decay_rate", 0.9)),
+        cc = _lib.CldMapCollision(ext.data_ptr(), rfa.data_ptr(), None if dm is None else dm.data_ptr(), spd.data_ptr(), start.data_ptr(),
+                                  wts.data_ptr(), len(sizes), N, H, W, nl, nw, float(c.get("decay_rate", 0.9)),
                                   float(c.get("guide_moving_speed_th", 0.5)))
         return cc, (ext, rfa, dm, spd, start, wts)
+
+    def _map_source(self, c: Mapping, B: int):
+        """The `map_source` of a map_collision dict `c` (see _map_collision) -> (CldMapSource, tensors kept alive).  Tensors already on
+        the device in the right type are read in place, as `rasterize` reads them."""
+        ms = c["map_source"]
+        N = int(c.get("num_samp", 1))
+        A = B // N
+        S = len(self._scene_blocks(c, A, "map_collision")[0])
+        if ms.get("world") is None:
+            raise CldError("map_collision: map_source needs world [A,3], the pose every agent's frame stands at")
+        world = self._f32(ms["world"], (A, 3))
+        mp = sm = mfw = None
+        num_maps = map_h = map_w = 0
+        n_sem = int(ms.get("n_sem", MAP_SOURCE_DEFAULTS["n_sem"]))
+        if ms.get("maps") is not None:
+            mp = self._f32(ms["maps"])
+            if mp.dim() != 4:
+                raise CldError(f"map_collision: map_source maps must be [num_maps,n_sem,map_h,map_w], got {tuple(mp.shape)}")
+            if "n_sem" in ms and mp.shape[1] != n_sem:
+                raise CldError(f"map_collision: map_source maps hold {mp.shape[1]} layers, n_sem = {n_sem}")
+            num_maps, n_sem, map_h, map_w = (int(v) for v in mp.shape)
+            if ms.get("scene_map") is None or ms.get("map_from_world") is None:
+                raise CldError("map_collision: map_source maps need scene_map and map_from_world")
+            sm = torch.as_tensor(ms["scene_map"]).to(self.device, torch.int32).contiguous()
+            if tuple(sm.shape) != (S,):
+                raise CldError(f"map_collision: map_source scene_map must be [{S}] (the term's scenes), got {tuple(sm.shape)}")
+            mfw = self._f32(ms["map_from_world"], (num_maps, 3, 3))
+        dp = lambda t: None if t is None else t.data_ptr()
+        ec = ms.get("ego_center", MAP_SOURCE_DEFAULTS["ego_center"])
+        src = _lib.CldMapSource(dp(mp), dp(sm), dp(mfw), world.data_ptr(), S, num_maps, n_sem, map_h, map_w, int(ms.get("drivable_layer", 0)),
+                                float(ms.get("px_per_m", MAP_SOURCE_DEFAULTS["px_per_m"])), (C.c_float * 2)(float(ec[0]), float(ec[1])),
+                                float(ms.get("no_map_fill", MAP_SOURCE_DEFAULTS["no_map_fill"])))
+        return src, (mp, sm, mfw, world)
+
+    @contextlib.contextmanager
+    def _map_source_term(self, mc: Optional[Mapping], B: int):
+        """The `map_source` of a map_collision dict kept on the handle for the library call inside (cld_set_map_source), and cleared
+        behind it whatever happens: no source outlives the call that set it."""
+        if mc is None or mc.get("map_source") is None:
+            yield
+            return
+        src, keep = self._map_source(mc, B)
+        self._check(self.lib.cld_set_map_source(self._h, C.byref(src)), "cld_set_map_source")
+        try:
+            yield
+        finally:
+            self.lib.cld_set_map_source(self._h, None)
 
     def _goal(self, c: Mapping, B: int):
         """dict(kind [A] (0 off | 1 global_target_pos | 2 global_target_pos_at_time, _lib.GOAL_KINDS), target_pos [A,2] (world),
@@ -530,7 +612,7 @@ class Engine:
         gi = None if grad_in is None else self._f32(grad_in, (B, T, 6))
         loss = torch.empty(B, dtype=torch.float32, device=self.device)
         grad = torch.empty(B, T, 6, dtype=torch.float32, device=self.device) if want_grad else None
-        with torch.cuda.device(self.device):
+        with torch.cuda.device(self.device), self._map_source_term(cfg, B):
             self._check(self.lib.cld_map_collision_loss(self._h, _ptr(traj), C.byref(cc), _ptr(gi), _ptr(loss), _ptr(grad), B, self._stream()),
                         "cld_map_collision_loss")
         return (loss, grad) if want_grad else loss
@@ -577,7 +659,7 @@ class Engine:
         xn = torch.empty_like(mean) if z is not None else None
         gr = torch.empty_like(mean) if want_grad else None
         ws, wsn = self._workspace(B)
-        with torch.cuda.device(self.device), self._goal_term(guidance, B):
+        with torch.cuda.device(self.device), self._goal_term(guidance, B), self._map_source_term((guidance or {}).get("map_collision"), B):
             self._check(self.lib.cld_guidance_step(self._h, _ptr(mean), _ptr(cond), C.byref(cg), C.c_float(sigma), _ptr(z),
                                                    _ptr(mg), _ptr(xn), _ptr(gr), B, ws, wsn, self._stream()), "cld_guidance_step")
         out = (mg,) + ((xn,) if z is not None else ()) + ((gr,) if want_grad else ())
@@ -638,7 +720,7 @@ class Engine:
         x1 = torch.empty_like(x_T) if (want_x1 and 1 in range(0, self.n_timesteps, self.stride)) else None
         logp = torch.empty(B, dtype=torch.float32, device=self.device) if want_logp else None
         cfg = non_cond is not None and guidance_w != 0.0
-        with torch.cuda.device(self.device), self._goal_term(guidance, B):
+        with torch.cuda.device(self.device), self._goal_term(guidance, B), self._map_source_term((guidance or {}).get("map_collision"), B):
             if guidance is not None:
                 cg, keep = self._guidance(guidance, B)
                 non_cond = self._f32(non_cond, (B, COND)) if cfg else None
@@ -678,7 +760,7 @@ class Engine:
         gr = torch.empty_like(x_t) if guided and want_grad else None
         ws, wsn = self._workspace(2 * ((B + 15) // 16 * 16) if cfg else B)
         sigma = C.c_float()
-        with torch.cuda.device(self.device), self._goal_term(guidance, B):
+        with torch.cuda.device(self.device), self._goal_term(guidance, B), self._map_source_term((guidance or {}).get("map_collision"), B):
             self._check(self.lib.cld_sample_step(self._h, _ptr(x_t), _ptr(cond), _ptr(non_cond), C.c_float(guidance_w),
                                                  None if cg is None else C.byref(cg), int(t_idx), _ptr(z), _ptr(xn), _ptr(mean),
                                                  _ptr(mg), _ptr(gr), C.byref(sigma), B, ws, wsn, self._stream()), "cld_sample_step")

@@ -14,10 +14,8 @@ from typing import Optional
 import torch
 
 from ._lib import CldError
+from .engine import RASTER_DEFAULTS, raster_frames      # (RASTER_DEFAULTS: config.yaml:81-86, :96)
 from .policy import frames_from_pose, invert_frames, transform_points
-
-RASTER_DEFAULTS = dict(height=224, width=224, px_per_m=2.0, ego_center=(-0.5, 0.0), no_map_fill=-1.0, max_neighbor_dist=30.0,
-                       n_sem=3)      # config.yaml:81-86, :96
 
 
 class SceneObserver:
@@ -57,6 +55,7 @@ class SceneObserver:
         if ss.numel() < 2 or int(ss[0]) != 0 or int(ss[-1]) != self.B_all or bool((ss[1:] <= ss[:-1]).any()):
             raise CldError(f"SceneObserver: scene_start {ss.tolist()} does not split the {self.B_all} agents into scenes")
         self.scene_start = ss.to(dev, torch.int32)
+        self._scene_bounds = ss                                    # (host copy: map_source() finds the scenes of this rank's rows)
         self.n_step_action = int(n_step_action)
         if not 1 <= self.n_step_action <= min(52, self.T_hist):
             raise CldError(f"SceneObserver: n_step_action = {n_step_action} (1 .. {min(52, self.T_hist)})")
@@ -72,9 +71,7 @@ class SceneObserver:
         self.scene_map = None if scene_map is None else torch.as_tensor(scene_map).to(dev, torch.int32).contiguous()
         self.map_from_world = None if map_from_world is None else torch.as_tensor(map_from_world).to(dev, torch.float32).contiguous()
         self.poses = self.hist_world[:, -1].clone()                # [B_all,3] world (x, y, h) now
-        H, W, ppm, ec = self.cfg["height"], self.cfg["width"], self.cfg["px_per_m"], self.cfg["ego_center"]
-        self.raster_from_agent = torch.tensor([[ppm, 0.0, (1.0 + ec[0]) / 2.0 * W], [0.0, ppm, (1.0 + ec[1]) / 2.0 * H], [0.0, 0.0, 1.0]],
-                                              dtype=torch.float32, device=dev)
+        self.raster_from_agent = raster_frames(self.cfg, 1)[0].to(dev)
         self._buf = None                                           # the reused image buffer of encode=True
 
     # ------------------------------------------------------------------ history
@@ -105,6 +102,17 @@ class SceneObserver:
         return {"history_positions": pos, "history_yaws": dyaw[..., None], "history_availabilities": av,
                 "raster_from_agent": rfa, "world_from_agent": W, "agent_from_world": M,
                 "agent_hist": torch.cat([pos, dyaw[..., None]], dim=-1)}
+
+    def map_source(self):
+        """The `map_source` of a map_collision term for this rank's rows (Engine._map_collision; `set_guidance(..., map_source=)`): the
+        observer's own maps and raster settings and the poses the agents stand at now.  A policy that follows the observation takes
+        the pose of every later step from the rollout.  `scene_map` holds the scenes this rank's rows lie in, in order -- the scenes a
+        term configured with these rows' scene_index has (a scene cut by the rank's boundary is one of them) -- not every rank's."""
+        first = int(torch.searchsorted(self._scene_bounds, self.row0, right=True)) - 1
+        last = int(torch.searchsorted(self._scene_bounds, self.row0 + self.B - 1, right=True)) - 1
+        scene_map = None if self.scene_map is None else self.scene_map[first:last + 1].contiguous()
+        return dict(self.cfg, maps=self.maps, scene_map=scene_map, map_from_world=self.map_from_world,
+                    world=self.poses[self.row0:self.row0 + self.B].clone(), drivable_layer=0)
 
     def _rasterize(self, row0, B, out=None):
         return self.engine.rasterize(self.hist_world, self.hist_avail, self.scene_start, self.maps, self.scene_map, self.map_from_world,

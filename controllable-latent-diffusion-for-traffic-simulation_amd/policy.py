@@ -23,6 +23,7 @@ import torch
 
 from ._lib import CldError
 from .dm_model import DmModel, repeat_guidance
+from .engine import raster_frames      # noqa: F401  (re-exported: the frames a map_source implies)
 from .vae_model import VaeModel
 
 
@@ -150,6 +151,41 @@ def update_goal_reached(reached, goal: Mapping, world_from_agent, agent_hist, by
     return reached
 
 
+def refresh_collision_terms(g: Optional[Mapping], obs: Mapping, world=None):
+    """The guidance dict `g` with the observation-dependent fields of its collision terms taken from `obs`, each only where `obs` holds
+    it -- what upstream's losses read from data_batch at every call (guidance_loss.py:506-510, :773-775):
+      agent_collision: world_from_agent, curr_speed
+      map_collision:   raster_from_agent, curr_speed, and drivable_map (raster mode) or map_source['world'] (map mode: `world` [B,3],
+                       default obs['world'], the pose the agents' frames stand at)
+    extent, weights, parameters and the scene structure stay as configured.  Nothing is modified in place; a dict without collision
+    terms comes back as it is."""
+    if g is None or (g.get("agent_collision") is None and g.get("map_collision") is None):
+        return g
+    out = dict(g)
+    speed = obs.get("curr_speed")
+    if g.get("agent_collision") is not None:
+        col = dict(g["agent_collision"])
+        if obs.get("world_from_agent") is not None:
+            col["world_from_agent"] = obs["world_from_agent"]
+        if speed is not None:
+            col["curr_speed"] = speed
+        out["agent_collision"] = col
+    if g.get("map_collision") is not None:
+        mcol = dict(g["map_collision"])
+        if obs.get("raster_from_agent") is not None:
+            mcol["raster_from_agent"] = obs["raster_from_agent"]
+        if speed is not None:
+            mcol["curr_speed"] = speed
+        if mcol.get("map_source") is not None:
+            pose = world if world is not None else obs.get("world")
+            if pose is not None:
+                mcol["map_source"] = dict(mcol["map_source"], world=pose)
+        elif obs.get("drivable_map") is not None:
+            mcol["drivable_map"] = obs["drivable_map"]
+        out["map_collision"] = mcol
+    return out
+
+
 class CldPolicy:
     def __init__(self, dm: DmModel, vae: VaeModel, context_encoder: Optional[Callable] = None,
                  disable_control_on_stationary: bool = False, moving_speed_th: float = 0.5, select_per_scene: bool = False):
@@ -160,6 +196,7 @@ class CldPolicy:
         self.select_per_scene = select_per_scene      # False = upstream's sample selection as written (see choose_action_from_guidance)
         self._guidance = None
         self._guidance_cfg = None                     # (guidance_config_list, scene_index) behind self._guidance
+        self._follow_observation = False              # set_guidance(follow_observation=True): the collision terms read every observation
         # closed-loop state of the goal losses (upstream keeps it on the loss objects): have_reached_mask [B], the rollout step of the
         # last get_action, and how the mask is updated ("any": the reference as written | "own", see update_goal_reached)
         self.goal_reached = None
@@ -172,12 +209,20 @@ class CldPolicy:
     def set_guidance(self, guidance_config_list, scene_index, **opt):
         """Upstream `set_guidance` (algos.py; guidance_loss.py:2106-2175): keep a guidance configuration for the following
         `get_action` calls.  `opt`: lr / optimizer / perturb_th of the optimiser step (scene_edit_config.py:74-90), `output`
-        (True | dict: guidance on the t = 0 output, upstream apply_guidance_output + final_step_opt_params), `intermediate`."""
+        (True | dict: guidance on the t = 0 output, upstream apply_guidance_output + final_step_opt_params), `intermediate`.
+        `follow_observation=True`: the collision terms take their frames, speeds and drivable map (or pose) from the observation of
+        every get_action, as upstream's losses read data_batch at every call (refresh_collision_terms); False (the default): they keep
+        what `data_batch` held here -- frozen frames.  `map_source` (dict: maps, scene_map, map_from_world, world, raster settings;
+        SceneObserver.map_source()): map_collision reads the scene maps instead of a per-agent drivable raster, and `data_batch` needs
+        only extent (and curr_speed) for it."""
         data_batch = opt.pop("data_batch", None)         # observation fields scene-coupled losses read (agent_collision: extent, world_from_agent, curr_speed)
+        follow = bool(opt.pop("follow_observation", False))
+        map_source = opt.pop("map_source", None)
         by = opt.pop("goal_reached_by", "any")
         if by not in ("any", "own"):
             raise ValueError(f"goal_reached_by={by!r} (any | own)")
-        self._guidance = dict(guidance_from_config(guidance_config_list, scene_index, data_batch=data_batch), **opt)
+        self._guidance = dict(guidance_from_config(guidance_config_list, scene_index, data_batch=data_batch, map_source=map_source), **opt)
+        self._follow_observation = follow
         self._guidance_cfg = (guidance_config_list, torch.as_tensor(scene_index).reshape(-1).cpu())
         # a new configuration starts with nobody arrived (upstream builds new loss objects: have_reached_mask = None)
         self.goal_reached_by = by
@@ -187,6 +232,7 @@ class CldPolicy:
     def clear_guidance(self):
         self._guidance = None
         self._guidance_cfg = None
+        self._follow_observation = False
         self.goal_reached = None
         self.goal_global_t = None
 
@@ -298,6 +344,8 @@ class CldPolicy:
         if g is not None and guide_clean:
             g = dict(g, guide_clean=True)
         from_cfg = g is self._guidance and self._guidance_cfg is not None
+        if guidance is None and self._follow_observation:           # the collision terms of set_guidance follow this observation
+            g = refresh_collision_terms(g, obs_dict)
         if g is not None and g.get("goal") is not None:
             carry = guidance is None
             g = dict(g, goal=self._goal_for_step(g["goal"], obs_dict, step_index, carry))
@@ -355,6 +403,9 @@ def closed_loop_rollout(policy: CldPolicy, cond_fn: Callable, centroid, yaw, cur
     `agent_from_world` [B,3,3] from the current world pose, and `agent_hist` [B,n_step_action,2]: the `n_step_action` executed states
     of the previous plan taken into the new agent frame (the last one is the agent's position now), on the first step the current
     position repeated.  `step_index` = the sim step is the goal losses' global_t.
+    With collision guidance that follows the observation (`set_guidance(..., follow_observation=True)`) the same holds for
+    `world_from_agent` (from the world pose), `curr_speed` (`curr_states[:, 2]`) and `world` [B,3], the pose itself, which a
+    map_collision term in map mode is evaluated at; a raster-mode term needs `drivable_map` from `cond_fn` (SceneObserver gives it).
     Returns the world poses after each sim step [n_sim_steps, B, 3]."""
     import inspect
     from contextlib import nullcontext
@@ -387,6 +438,15 @@ def closed_loop_rollout(policy: CldPolicy, cond_fn: Callable, centroid, yaw, cur
                     if "agent_hist" not in obs:
                         hw = world[:, None, :2].expand(-1, n_step_action, -1) if hist_world is None else hist_world
                         obs["agent_hist"] = transform_points(hw, torch.as_tensor(obs["agent_from_world"]).float().to(hw.device))
+                pg = policy._guidance or {}
+                if gk is None and policy._follow_observation and (pg.get("agent_collision") is not None or pg.get("map_collision") is not None):
+                    obs = dict(obs)                   # the collision terms follow the observation: what cond_fn's lacks, from the loop's own state
+                    if "world_from_agent" not in obs:
+                        obs["world_from_agent"] = frames_from_pose(world)
+                    if "curr_speed" not in obs:
+                        obs["curr_speed"] = cs[:, 2].contiguous()
+                    if "world" not in obs:
+                        obs["world"] = world
             with tm("network"):
                 _, info = policy.get_action(obs, step_index=step, **get_action_kwargs)
                 traj = info["executed_trajectory"].contiguous()
@@ -406,7 +466,8 @@ def closed_loop_rollout(policy: CldPolicy, cond_fn: Callable, centroid, yaw, cur
     return torch.stack(poses)
 
 
-def guidance_from_config(guidance_config_list, scene_index, horizon: int = 52, data_batch: Optional[Mapping] = None) -> dict:
+def guidance_from_config(guidance_config_list, scene_index, horizon: int = 52, data_batch: Optional[Mapping] = None,
+                         map_source: Optional[Mapping] = None) -> dict:
     """Upstream's guidance configuration -> the `guidance=` dict of `DmModel.forward` / `Engine.sample`.
 
     `guidance_config_list` is what `DiffuserTrafficModel.set_guidance` takes (`src/tbsim/algos/algos.py`, built by
@@ -416,7 +477,9 @@ def guidance_from_config(guidance_config_list, scene_index, horizon: int = 52, d
     per-agent scales of the kernel: weight / (agents * horizon) for the per-step losses, weight / agents for the waypoint
     losses.  Supported names: target_speed, speed_limit, acc_limit, target_pos_at_time, target_pos, agent_collision (needs
     `data_batch` with `extent`, `world_from_agent`, `curr_speed`: the observation fields upstream's loss reads,
-    guidance_loss.py:506-510), map_collision (`extent`, `raster_from_agent`, `drivable_map`, `curr_speed`, :773-775) and the world-frame
+    guidance_loss.py:506-510), map_collision (`extent`, `raster_from_agent`, `drivable_map`, `curr_speed`, :773-775; with `map_source`
+    -- Engine._map_collision -- the entry carries that instead of a drivable_map, `data_batch` needs only `extent` (and `curr_speed`,
+    unless every get_action's observation brings it) and raster_from_agent defaults to the source's raster settings) and the world-frame
     waypoint losses global_target_pos / global_target_pos_at_time (:930-1135; params target_pos, target_time, urgency, pref_speed = 1.42,
     dt = 0.1, min_progress_dist = 0.5, target_tolerance = None / 2, action_num = 5, all indexed by the config's `agents`; scale =
     weight / agents; at most one per agent, one dt and one min_progress_dist per call); at most
@@ -486,15 +549,24 @@ def guidance_from_config(guidance_config_list, scene_index, horizon: int = 52, d
                     mem = set(int(b) for b in members)
                     col.setdefault("excluded_agents", []).extend(int(b) for b in prm["excluded_agents"] if int(b) in mem)
             elif name == "map_collision":
-                need = ("extent", "raster_from_agent", "drivable_map", "curr_speed")
-                if data_batch is None or any(k not in data_batch for k in need):
-                    raise ValueError("map_collision needs data_batch with extent, raster_from_agent, drivable_map and curr_speed")
+                if map_source is None:
+                    need = ("extent", "raster_from_agent", "drivable_map", "curr_speed")
+                    if data_batch is None or any(k not in data_batch for k in need):
+                        raise ValueError("map_collision needs data_batch with extent, raster_from_agent, drivable_map and curr_speed")
+                    fields = {k: data_batch[k] for k in need}
+                else:
+                    if data_batch is None or "extent" not in data_batch:
+                        raise ValueError("map_collision with a map_source needs data_batch with extent")
+                    rfa = data_batch["raster_from_agent"] if "raster_from_agent" in data_batch else raster_frames(map_source, B)
+                    fields = dict(extent=data_batch["extent"], raster_from_agent=rfa, map_source=dict(map_source))
+                    if "curr_speed" in data_batch:
+                        fields["curr_speed"] = data_batch["curr_speed"]
                 if agents is not None:
                     raise NotImplementedError("map_collision on an `agents` subset (upstream itself cannot run it: guidance_loss.py:857-859)")
                 S = int(local.max()) + 1
                 key = (tuple(int(v) for v in prm.get("num_points_lw", (10, 10))), float(prm.get("decay_rate", 0.9)), float(prm.get("guide_moving_speed_th", 0.5)))
                 if mcol is None:
-                    mcol = dict({k: data_batch[k] for k in need}, scene_index=scene_index, weight=[0.0] * S, num_points_lw=key[0], decay_rate=key[1],
+                    mcol = dict(fields, scene_index=scene_index, weight=[0.0] * S, num_points_lw=key[0], decay_rate=key[1],
                                 guide_moving_speed_th=key[2])
                 elif (tuple(mcol["num_points_lw"]), mcol["decay_rate"], mcol["guide_moving_speed_th"]) != key:
                     raise ValueError("one map_collision parameter set per call")

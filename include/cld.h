@@ -278,7 +278,7 @@ int cld_agent_collision(cld_handle h, const float* traj, const cld_collision* c,
 typedef struct cld_map_collision {
     const float* extent;             /* DEVICE [A,3]                                           */
     const float* raster_from_agent;  /* DEVICE [A,3,3] row-major                               */
-    const uint8_t* drivable_map;     /* DEVICE [A,H,W], non-zero = drivable                    */
+    const uint8_t* drivable_map;     /* DEVICE [A,H,W], non-zero = drivable; NULL: cld_set_map_source */
     const float* curr_speed;         /* DEVICE [A]                                             */
     const int32_t* scene_start;      /* DEVICE [num_scenes + 1]                                */
     const float* scene_weight;       /* DEVICE [num_scenes], 0 = scene not guided              */
@@ -294,6 +294,29 @@ typedef struct cld_map_collision {
  * (+ grad_in when given; grad_in may be grad itself).  Either output may be NULL. */
 int cld_map_collision_loss(cld_handle h, const float* traj, const cld_map_collision* c, const float* grad_in, float* loss,
                            float* grad, int32_t B, void* stream);
+
+/* The map term without a per-agent raster: the scene's semantic maps, kept on the handle (the struct is copied by value; NULL clears it).
+ * While a source is set, a cld_map_collision with drivable_map == NULL is legal -- in cld_map_collision_loss and, as a term, in
+ * cld_guidance_step, cld_sample_step and cld_sample_guided -- and the flag of raster pixel (ix, iy) of agent a is drv(a; ix, iy) as defined
+ * for cld_scene_metrics below, evaluated at the pose world[a]: the byte cld_rasterize writes to drivable[a, iy, ix] for an agent standing
+ * there with this px_per_m / ego_center / no_map_fill and height, width = the term's H, W -- bit for bit, layer `drivable_layer` in place of
+ * plane 0.  (ix, iy) is raster_from_agent applied to the sample point, truncated and clamped to H x W, exactly as in raster mode.  The map
+ * of agent a is scene_map[s], s = a's scene in the term's OWN scene_start; num_scenes must agree with the term's (CLD_ERR_ARG).  Off
+ * road = the map value == 0; a pixel outside the map, a scene with scene_map < 0 (or >= num_maps) and maps == NULL take no_map_fill
+ * under the same rule, so the default fill of -1 is drivable.  world is read at every launch: refresh it (or set the source anew) when
+ * the agents have moved.  With a non-NULL drivable_map the source is ignored and the results are what they are without one.  Without a
+ * source drivable_map == NULL is CLD_ERR_ARG.  CLD_ERR_ARG at set time (nothing is skipped silently): NULL world, num_scenes < 1,
+ * px_per_m <= 0, drivable_layer outside [0, n_sem), maps without their companions.  (A setter and not a field of cld_map_collision:
+ * that struct's layout is frozen.) */
+typedef struct cld_map_source {
+    const float*   maps;            /* DEVICE [num_maps, n_sem, map_h, map_w] or NULL */
+    const int32_t* scene_map;       /* DEVICE [num_scenes], < 0: no map (everything takes no_map_fill) */
+    const float*   map_from_world;  /* DEVICE [num_maps,3,3] */
+    const float*   world;           /* DEVICE [A,3] (x, y, h): the pose agent a's frame stands at */
+    int32_t num_scenes, num_maps, n_sem, map_h, map_w, drivable_layer;
+    float   px_per_m, ego_center[2], no_map_fill;
+} cld_map_source;
+int cld_set_map_source(cld_handle h, const cld_map_source* m);   /* NULL clears */
 
 /* Upstream's GlobalTargetPosLoss (`global_target_pos`) and GlobalTargetPosAtTimeLoss (`global_target_pos_at_time`),
  * src/tbsim/utils/guidance_loss.py:876-1135: a waypoint in the WORLD frame, taken into the agent frame of the current plan
