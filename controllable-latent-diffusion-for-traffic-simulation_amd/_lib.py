@@ -169,6 +169,12 @@ SIGNATURES = {
     "cld_scene_metrics_state_bytes": (C.c_size_t, [C.c_int32]),
     "cld_scene_metrics_step": (C.c_int, [_P, C.POINTER(CldSceneMetrics), _P, _P, _P, _P, C.c_int32, _P]),
     "cld_scene_metrics_read": (C.c_int, [_P, C.POINTER(CldSceneMetrics), _P, _P, _P, _P]),
+    "cld_sort_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "cld_sort_f32": (C.c_int, [_P, _P, _P, C.c_int64, _P, C.c_size_t, _P]),
+    "cld_wasserstein_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "cld_wasserstein_f32": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, _P, _P, C.c_size_t, _P]),
+    "cld_realism_terms": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_float, _P, _P, _P, _P]),
+    "cld_debug_sort_items_per_block": (C.c_int32, []),
     "cld_profile_enable": (C.c_int, [_P, C.c_int32]),
     "cld_profile_read": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
     "cld_profile_read_executed": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32)]),

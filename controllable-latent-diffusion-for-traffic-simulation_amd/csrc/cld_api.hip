@@ -2142,6 +2142,47 @@ int cld_scene_metrics_read(cld_handle h, const cld_scene_metrics* m, const void*
     return CLD_OK;
 }
 
+/* ---- realism deviation: terms, fp32 sort, Wasserstein-1 (realism_kernels.hip) ---- */
+int32_t cld_debug_sort_items_per_block(void) { return SORT_TILE; }
+
+size_t cld_sort_workspace_bytes(int64_t n) { return n < 1 || n > SORT_MAX_N ? 0 : sort_ws_bytes(n); }
+
+int cld_sort_f32(cld_handle h, const float* in, float* out, int64_t n, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!h) return CLD_ERR_ARG;
+    if (!in || !out) return fail(h, CLD_ERR_ARG, "cld_sort_f32: null pointer");
+    if (n < 1 || n > SORT_MAX_N) return fail(h, CLD_ERR_ARG, "cld_sort_f32: n must be in [1, 2^30]");
+    if (!workspace || workspace_bytes < sort_ws_bytes(n)) return fail(h, CLD_ERR_WORKSPACE, "cld_sort_f32: workspace too small");
+    if (reinterpret_cast<uintptr_t>(workspace) % 16) return fail(h, CLD_ERR_ARG, "cld_sort_f32: workspace must be 16-byte aligned");
+    HIPCK(h, launch_sort_f32(in, out, n, workspace, static_cast<hipStream_t>(stream)));
+    return CLD_OK;
+}
+
+size_t cld_wasserstein_workspace_bytes(int64_t nu, int64_t nv) {
+    return nu < 1 || nv < 1 || nu > SORT_MAX_N || nv > SORT_MAX_N ? 0 : (size_t)w1_tiles(nu, nv) * sizeof(double);
+}
+
+int cld_wasserstein_f32(cld_handle h, const float* u_sorted, int64_t nu, const float* v_sorted, int64_t nv, double* out, void* workspace,
+                        size_t workspace_bytes, void* stream) {
+    if (!h) return CLD_ERR_ARG;
+    if (!u_sorted || !v_sorted || !out) return fail(h, CLD_ERR_ARG, "cld_wasserstein_f32: null pointer");
+    if (nu < 1 || nv < 1 || nu > SORT_MAX_N || nv > SORT_MAX_N) return fail(h, CLD_ERR_ARG, "cld_wasserstein_f32: nu and nv must be in [1, 2^30]");
+    if (!workspace || workspace_bytes < cld_wasserstein_workspace_bytes(nu, nv))
+        return fail(h, CLD_ERR_WORKSPACE, "cld_wasserstein_f32: workspace too small");
+    if (reinterpret_cast<uintptr_t>(workspace) % 8 || reinterpret_cast<uintptr_t>(out) % 8)
+        return fail(h, CLD_ERR_ARG, "cld_wasserstein_f32: out and workspace must be 8-byte aligned");
+    HIPCK(h, launch_wasserstein_f32(u_sorted, nu, v_sorted, nv, out, workspace, static_cast<hipStream_t>(stream)));
+    return CLD_OK;
+}
+
+int cld_realism_terms(cld_handle h, const float* sa, int64_t M, int32_t T, float dt, float* lon, float* lat, float* jerk, void* stream) {
+    if (!h) return CLD_ERR_ARG;
+    if (!sa || (!lon && !lat && !jerk)) return fail(h, CLD_ERR_ARG, "cld_realism_terms: null pointer (sa, or no output)");
+    if (M < 1 || T < 2 || M > SORT_MAX_N / T) return fail(h, CLD_ERR_ARG, "cld_realism_terms: needs M >= 1, T >= 2 and M T <= 2^30");
+    if (!(dt > 0.f) || !(dt < INFINITY)) return fail(h, CLD_ERR_ARG, "cld_realism_terms: dt must be positive and finite");
+    HIPCK(h, launch_realism_terms(sa, M, T, dt, lon, lat, jerk, static_cast<hipStream_t>(stream)));
+    return CLD_OK;
+}
+
 /* ---- training: what the U-Net and the LSTM-VAE entry points share ---- */
 static int param_info(cld_handle h, const char* fn, const TrainParam* table, int count, int32_t i, const char** name, size_t* offset,
                       size_t* numel, int32_t* shape, int32_t* ndim) {

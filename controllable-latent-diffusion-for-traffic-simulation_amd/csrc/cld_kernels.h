@@ -332,6 +332,20 @@ struct MetricsArgs {
 hipError_t launch_scene_metrics_step(const MetricsArgs& a, hipStream_t s);
 hipError_t launch_scene_metrics_read(const MetricsArgs& a, hipStream_t s);
 
+// the realism deviation (realism_kernels.hip; src/trainers/guide_dm_trainer.py:204-295): the compared quantities, an fp32 sort and the
+// Wasserstein-1 distance of two sorted samples.  The sort works on tiles of SORT_TILE keys; its workspace is a second copy of the keys
+// (rounded up to 256 bytes), the digit counts hist[256][tiles] and the 256 digit totals.  The distance leaves one fp64 partial per tile
+// of W1_TILE terms (paired: elements; CDF form: consecutive pairs of the merged sequence).
+constexpr int SORT_TILE = 4096, W1_TILE = 2048;
+constexpr int64_t SORT_MAX_N = (int64_t)1 << 30;
+inline int64_t sort_tiles(int64_t n) { return (n + SORT_TILE - 1) / SORT_TILE; }
+inline size_t sort_tmp_bytes(int64_t n) { return ((size_t)n * 4 + 255) / 256 * 256; }
+inline size_t sort_ws_bytes(int64_t n) { return sort_tmp_bytes(n) + ((size_t)sort_tiles(n) * 256 + 256) * 4; }
+inline int64_t w1_tiles(int64_t nu, int64_t nv) { return ((nu == nv ? nu : nu + nv - 1) + W1_TILE - 1) / W1_TILE; }
+hipError_t launch_realism_terms(const float* sa, int64_t M, int T, float dt, float* lon, float* lat, float* jerk, hipStream_t s);
+hipError_t launch_sort_f32(const float* in, float* out, int64_t n, void* ws, hipStream_t s);
+hipError_t launch_wasserstein_f32(const float* u, int64_t nu, const float* v, int64_t nv, double* out, void* ws, hipStream_t s);
+
 // ---- ContextEncoder (models/context_utils.py:8-61; context_kernels.hip) ------------------------------------
 // stem: image [B,34,224,224] NCHW -> y [B,112,112,64] NHWC = ReLU(BN(conv 7x7/2)); wq: packed by pack_stem_weights
 // pooled != null: MaxPool2d(3, 2, 1) fused (y unused): pooled [B,56,56,64] NHWC, zero-filled by the launcher, completed by atomic max

@@ -110,8 +110,8 @@ class Engine:
             rc = self.lib.cld_create(C.byref(cfg), C.byref(self._h))
         if rc != 0:
             raise CldError(f"cld_create failed ({rc})")
-        self._ws = self._ctx_ws = self._tws = self._vws = None      # grow-only device scratch (_scratch): sampling, ContextEncoder,
-                                                                    # U-Net training, VAE training
+        self._ws = self._ctx_ws = self._tws = self._vws = self._rws = None      # grow-only device scratch (_scratch): sampling, ContextEncoder,
+                                                                                # U-Net training, VAE training, sort / Wasserstein
         self._nc_map_feat = {}
         self._finalized = False
         self.precision = {v: k for k, v in _lib.PRECISIONS.items()}[int(self.lib.cld_get_precision(self._h))]
@@ -1152,6 +1152,64 @@ class Engine:
             self._check(self.lib.cld_scene_metrics_read(self._h, C.byref(st), _ptr(state), _ptr(per_agent), _ptr(per_scene),
                                                         self._stream()), "cld_scene_metrics_read")
         return per_agent, per_scene
+
+    # ------------------------------------------------------------------ realism deviation (guide_dm_trainer.py:204-295)
+    def _flat_f32(self, t, what: str) -> torch.Tensor:
+        t = self._f32(t).reshape(-1)
+        if t.numel() < 1:
+            raise CldError(f"{what}: needs at least one value")
+        return t
+
+    def sort(self, values, out: Optional[torch.Tensor] = None):
+        """The values ascending in numpy's order (NaN last; cld_sort_f32), flattened.  `out`: a contiguous fp32 device tensor of the same
+        count to write to; it may be `values` itself (in place).  No host synchronisation."""
+        x = self._flat_f32(values, "sort")
+        n = x.numel()
+        if out is None:
+            out = torch.empty_like(x)
+        elif not (isinstance(out, torch.Tensor) and out.device == self.device and out.dtype == torch.float32 and out.is_contiguous()
+                  and out.numel() == n):
+            raise CldError(f"sort: out must be a contiguous fp32 tensor of {n} values on {self.device}")
+        ws, wsn = self._scratch("_rws", int(self.lib.cld_sort_workspace_bytes(n)))
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cld_sort_f32(self._h, _ptr(x), _ptr(out), n, ws, wsn, self._stream()), "cld_sort_f32")
+        return out.reshape(-1)
+
+    def wasserstein_distance(self, u, v, presorted: bool = False):
+        """scipy.stats.wasserstein_distance(u, v) of two fp32 samples (cld_wasserstein_f32) -> a 0-d float64 device tensor.  With
+        `presorted` both are taken as ascending already (Engine.sort's or np.sort's order).  No host synchronisation."""
+        u, v = self._flat_f32(u, "wasserstein_distance"), self._flat_f32(v, "wasserstein_distance")
+        if not presorted:
+            u, v = self.sort(u), self.sort(v)
+        out = torch.empty((), dtype=torch.float64, device=self.device)
+        ws, wsn = self._scratch("_rws", int(self.lib.cld_wasserstein_workspace_bytes(u.numel(), v.numel())))
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cld_wasserstein_f32(self._h, _ptr(u), u.numel(), _ptr(v), v.numel(), _ptr(out), ws, wsn, self._stream()),
+                        "cld_wasserstein_f32")
+        return out
+
+    def realism_terms(self, sa, dt: float, out=None):
+        """sa [M,T,6] (scaled state and action) -> (long_acc [M T], lat_acc [M T], jerk [M (T-1)]) as test_step forms them
+        (cld_realism_terms).  `out`: three contiguous fp32 device tensors (or None: not wanted) of at least those counts to write into."""
+        sa = self._f32(sa)
+        if sa.dim() != 3 or sa.shape[2] != 6 or sa.shape[0] < 1 or sa.shape[1] < 2:
+            raise CldError(f"realism_terms: expected [M >= 1, T >= 2, 6], got {tuple(sa.shape)}")
+        M, T = int(sa.shape[0]), int(sa.shape[1])
+        counts = (M * T, M * T, M * (T - 1))
+        if out is None:
+            out = tuple(torch.empty(c, dtype=torch.float32, device=self.device) for c in counts)
+        else:
+            out = tuple(out)
+            if len(out) != 3 or all(o is None for o in out):
+                raise CldError("realism_terms: out must be three tensors, at least one of them not None")
+            for o, c in zip(out, counts):
+                if o is not None and not (isinstance(o, torch.Tensor) and o.device == self.device and o.dtype == torch.float32
+                                          and o.is_contiguous() and o.numel() >= c):
+                    raise CldError(f"realism_terms: an output must be a contiguous fp32 tensor of at least {c} values on {self.device}")
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cld_realism_terms(self._h, _ptr(sa), M, T, float(dt), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]),
+                                                   self._stream()), "cld_realism_terms")
+        return out
 
     # ------------------------------------------------------------------ measurement
     def profile_enable(self, on: bool = True):

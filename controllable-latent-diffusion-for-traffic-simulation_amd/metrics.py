@@ -5,6 +5,10 @@ CollisionRate, DiskCollisionRate, CriticalFailure, Comfort of src/tbsim/envs/env
 The arithmetic is `cld_scene_metrics_step` / `cld_scene_metrics_read` (csrc/metrics_kernels.hip; include/cld.h defines every
 quantity).  The bookkeeping here is the state buffer, the step counter and the poses, which move with `cld_world_step` exactly as
 `SceneObserver.advance` moves its own, so the scored poses are the observer's history frames bit for bit.
+
+`RealismDeviation` is the test stage's other number (src/trainers/guide_dm_trainer.py:204-295): the mean Wasserstein-1 distance between
+ground truth and prediction of three quantities, accumulated and evaluated on the device (`cld_realism_terms`, `cld_sort_f32`,
+`cld_wasserstein_f32`; csrc/realism_kernels.hip).
 """
 from __future__ import annotations
 
@@ -95,3 +99,83 @@ class RolloutMetrics:
             "all_failure": {"failure_offroad": s[:, 9], "failure_collision": s[:, 10], "failure_any": s[:, 11]},
             "all_comfort": {"speed": s[:, 12], "lon_acc": s[:, 13], "lat_acc": s[:, 14], "jerk": s[:, 15]},
         }
+
+
+class RealismDeviation:
+    """The realism deviation of the reference's test stage (src/trainers/guide_dm_trainer.py:204-295) on the device: the mean of the
+    Wasserstein-1 distances between ground truth and prediction of the longitudinal acceleration, the lateral acceleration and the jerk
+    of scaled [M,T,6] trajectories.  Six grow-by-doubling device buffers hold the values fed since `reset()`; their fill counts follow
+    from the shapes and live on the host, so `add` issues no synchronisation.  `dt` is the config's step_time; `capacity` the values
+    each buffer holds before it first grows.
+
+    Upstream's `test_step` re-creates its list on every call, so its epoch value covers the LAST batch only; this accumulator covers
+    everything fed since `reset()`.  `reset()` before every `add` reproduces upstream."""
+
+    SIDES = ("gt", "pred")
+    NAMES = ("lon", "lat", "jerk")
+
+    def __init__(self, engine, dt: float = 0.1, capacity: int = 0):
+        if not float(dt) > 0.0:
+            raise CldError(f"RealismDeviation: dt = {dt} must be positive")
+        self.engine = engine
+        self.dt = float(dt)
+        cap = max(int(capacity), 0)
+        self._buf = {(s, n): torch.empty(cap, dtype=torch.float32, device=engine.device) for s in self.SIDES for n in self.NAMES}
+        self._fill = {k: 0 for k in self._buf}
+
+    def reset(self):
+        """Empty the six buffers (their memory is kept)."""
+        for k in self._fill:
+            self._fill[k] = 0
+
+    def _tail(self, key, count: int):
+        """The next `count` slots of buffer `key`, after growing it (doubling, at least to fit) when they would overflow it."""
+        buf, fill = self._buf[key], self._fill[key]
+        if fill + count > buf.numel():
+            grown = torch.empty(max(2 * buf.numel(), fill + count), dtype=torch.float32, device=self.engine.device)
+            grown[:fill].copy_(buf[:fill])
+            self._buf[key] = buf = grown
+        return buf[fill:fill + count]
+
+    def add(self, sa_gt, sa_pred):
+        """One batch as `test_step` sees it: sa_gt = state_and_action, sa_pred = recon_state_and_action_scaled, each [M,T,6] scaled (the
+        two may differ in M).  The terms kernel writes straight into the buffers' tails."""
+        both = [self.engine._f32(sa) for sa in (sa_gt, sa_pred)]
+        for sa in both:                                            # both sides are checked before either is appended
+            if sa.dim() != 3 or sa.shape[2] != 6 or sa.shape[0] < 1 or sa.shape[1] < 2:
+                raise CldError(f"RealismDeviation.add: expected [M >= 1, T >= 2, 6], got {tuple(sa.shape)}")
+        for side, sa in zip(self.SIDES, both):
+            M, T = int(sa.shape[0]), int(sa.shape[1])
+            counts = dict(lon=M * T, lat=M * T, jerk=M * (T - 1))
+            self.engine.realism_terms(sa, self.dt, out=tuple(self._tail((side, n), counts[n]) for n in self.NAMES))
+            for n in self.NAMES:
+                self._fill[(side, n)] += counts[n]
+
+    def add_values(self, side: str, lon=None, lat=None, jerk=None):
+        """Append ready-made values to one side ("gt" or "pred"): a closed loop compares simulated values with logged ones of another
+        count this way."""
+        if side not in self.SIDES:
+            raise ValueError(f"RealismDeviation.add_values: side must be one of {self.SIDES}, got {side!r}")
+        for n, vals in zip(self.NAMES, (lon, lat, jerk)):
+            if vals is None:
+                continue
+            vals = self.engine._f32(vals).reshape(-1)
+            if vals.numel():
+                self._tail((side, n), vals.numel()).copy_(vals)
+                self._fill[(side, n)] += vals.numel()
+
+    def values(self):
+        """-> {"gt": {"lon", "lat", "jerk"}, "pred": {...}}: the filled part of the six buffers (views).  A multi-rank caller all-gathers
+        them and feeds another instance with `add_values`."""
+        return {s: {n: self._buf[(s, n)][:self._fill[(s, n)]] for n in self.NAMES} for s in self.SIDES}
+
+    def compute(self):
+        """`on_test_epoch_end`: {"wd_long", "wd_lat", "wd_jerk", "realism_deviation"} as 0-d float64 device tensors: six sorts, three
+        distances and their mean, all on the device.  The buffers are left as they are."""
+        v = self.values()
+        empty = [f"{s}/{n}" for s in self.SIDES for n in self.NAMES if v[s][n].numel() == 0]
+        if empty:
+            raise ValueError(f"RealismDeviation.compute: no values in {empty}")
+        e = self.engine
+        wd = [e.wasserstein_distance(e.sort(v["gt"][n]), e.sort(v["pred"][n]), presorted=True) for n in self.NAMES]
+        return {"wd_long": wd[0], "wd_lat": wd[1], "wd_jerk": wd[2], "realism_deviation": (wd[0] + wd[1] + wd[2]) / 3.0}

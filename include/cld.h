@@ -581,6 +581,51 @@ int cld_scene_metrics_read(cld_handle h, const cld_scene_metrics* m, const void*
                            float* per_agent /*[B_all, CLD_METRICS_AGENT_COLS] or NULL*/,
                            float* per_scene /*[num_scenes, CLD_METRICS_SCENE_COLS] or NULL*/, void* stream);
 
+/* The realism deviation of the test stage (src/trainers/guide_dm_trainer.py:204-295): the mean of three Wasserstein-1 distances between
+ * ground-truth and predicted samples of the longitudinal acceleration, the lateral acceleration and the jerk.  Three primitives; none
+ * needs weights, none depends on the handle's precision mode (plain fp32 / fp64 in both), none synchronises.  All pointers are DEVICE.
+ *
+ * cld_realism_terms: sa [M, T, 6] fp32 (x, y, vel, yaw, acc, yawvel; scaled, as test_step compares them) ->
+ *   lon [M T]        = sa[m, t, 4]                                           (a copy)
+ *   lat [M T]        = sa[m, t, 2] * sa[m, t, 5]                             (one fp32 product)
+ *   jerk [M (T - 1)] = (sa[m, t + 1, 4] - sa[m, t, 4]) / dt, t < T - 1       (one fp32 difference, one correctly rounded fp32 division by
+ *                                                                             dt; no reciprocal, no contraction)
+ * each flattened row-major, written at the given destinations (an accumulator hands its buffers' tails).  Any of the three may be
+ * NULL and is then not written; all three NULL is CLD_ERR_ARG.  Needs M >= 1, T >= 2, M T <= 2^30, 0 < dt < inf (else CLD_ERR_ARG).
+ *
+ * cld_sort_f32: out [n] = the n values of `in` ascending, key only, in numpy's order: -inf first, +inf before NaN, every NaN of
+ * either sign last; -0.0 sorts before +0.0 (np.sort leaves equal keys in either order); denormals are ordered by value, not flushed.
+ * Values are moved as bits, except that every NaN comes out as the quiet NaN 0x7fffffff.  The output is a function of the input values
+ * alone: a stable LSD radix sort over the monotone integer image of the key, no atomics on global memory.  out == in is allowed;
+ * any other overlap of the two, or of either with the workspace, is not.  1 <= n <= 2^30 (else CLD_ERR_ARG);
+ * workspace >= cld_sort_workspace_bytes(n) bytes, 16-byte aligned (a second copy of the keys plus 1 KiB of digit counts per
+ * cld_debug_sort_items_per_block() keys; 0 for an n out of range), else CLD_ERR_WORKSPACE.
+ *
+ * cld_wasserstein_f32: *out (fp64, 8-byte aligned) = the 1-D Wasserstein-1 distance of the empirical distributions of u_sorted [nu] and
+ * v_sorted [nv], both ascending in cld_sort_f32's (or np.sort's) order: scipy.stats.wasserstein_distance without weights.
+ *   nu == nv = n: (1 / n) sum_i |u_i - v_i|.
+ *   nu != nv:     with a_0 <= ... <= a_{N-1} the merged values, N = nu + nv, cu_k and cv_k the numbers of values of u and v that are <= a_k,
+ *                 (1 / (nu nv)) sum_k |cu_k nv - cv_k nu| (a_{k+1} - a_k) over the k with a_{k+1} != a_k.  A run of equal values -- inside
+ *                 one sample or across both, -0 and +0 included -- contributes only at its last element, where the counts are the
+ *                 inclusive ones: the right-continuous CDFs scipy evaluates.  The counts are integers (exact below 2^60).
+ * Every difference and sum is fp64.  Each workgroup leaves one partial in the workspace, summed in a fixed order, and one workgroup folds the
+ * partials in a fixed order and divides once: the result is bit-identical from run to run.  With every term non-negative its relative
+ * error is within (nu + nv) 2^-53 of the exact sum of the rounded terms.  A NaN in either sample, or an inf - inf between neighbours,
+ * gives NaN, as numpy's arithmetic does; that is not an error.  1 <= nu, nv <= 2^30 (else CLD_ERR_ARG);
+ * workspace >= cld_wasserstein_workspace_bytes(nu, nv) bytes, 8-byte aligned (0 for sizes out of range), else CLD_ERR_WORKSPACE.
+ * Unsorted input is not detected: the result is then meaningless (memory stays in bounds).
+ *
+ * NULL sa / in / out / u_sorted / v_sorted: CLD_ERR_ARG.  Nothing is skipped silently.
+ * cld_debug_sort_items_per_block: the keys one workgroup of the sort ranks (no handle, no device call; tests straddle it). */
+size_t cld_sort_workspace_bytes(int64_t n);
+int cld_sort_f32(cld_handle h, const float* in, float* out, int64_t n, void* workspace, size_t workspace_bytes, void* stream);
+size_t cld_wasserstein_workspace_bytes(int64_t nu, int64_t nv);
+int cld_wasserstein_f32(cld_handle h, const float* u_sorted, int64_t nu, const float* v_sorted, int64_t nv, double* out,
+                        void* workspace, size_t workspace_bytes, void* stream);
+int cld_realism_terms(cld_handle h, const float* sa /*[M,T,6]*/, int64_t M, int32_t T, float dt, float* lon /*[M T] or NULL*/,
+                      float* lat /*[M T] or NULL*/, float* jerk /*[M (T-1)] or NULL*/, void* stream);
+int32_t cld_debug_sort_items_per_block(void);
+
 /* Which form a Conv1d(k5) + GroupNorm + Mish launch takes (no handle, no device call; tests): CLD_FORM_WINOGRAD or CLD_FORM_DIRECT for a
  * layer with `c1` (+ `c2` concatenated) input channels, `c_out` output channels and `l_in` rows per agent in a launch set of `rows` agents
  * (padded to 16 inside), with `forced_form` = what cld_debug_force_kernel(CLD_KERNEL_CONV5, ...) would hold (CLD_FORM_AUTO: by size).
