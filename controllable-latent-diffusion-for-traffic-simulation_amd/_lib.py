@@ -119,6 +119,18 @@ class CldSceneMetrics(C.Structure):
                 ("px_per_m", C.c_float), ("ego_center", C.c_float * 2), ("no_map_fill", C.c_float)]
 
 
+class CldOccupancy(C.Structure):
+    """include/cld.h `cld_occupancy` (one occupancy grid over a scene set: windows, cell offsets, map and kernel settings, device pointers)."""
+    _fields_ = [("scene_start", C.c_void_p), ("window", C.c_void_p), ("cell_start", C.c_void_p), ("maps", C.c_void_p),
+                ("scene_map", C.c_void_p), ("map_from_world", C.c_void_p), ("cells", C.c_int64),
+                ("offset", C.c_double * 2), ("step", C.c_double * 2), ("sigma", C.c_double), ("kernel_cut", C.c_double),
+                ("num_scenes", C.c_int32), ("B_all", C.c_int32), ("n_sem", C.c_int32), ("num_maps", C.c_int32), ("map_h", C.c_int32),
+                ("map_w", C.c_int32), ("drivable_layer", C.c_int32), ("no_map_fill", C.c_float)]
+
+
+OCCUPANCY_MAX_WINDOW_CELLS = 1024      # include/cld.h CLD_OCCUPANCY_MAX_WINDOW_CELLS
+OCCUPANCY_Q = float(1 << 40)           # the grid planes are Q40 fixed point
+
 METRICS_AGENT_COLS = ("steps", "steps_valid", "off_road_sum", "off_road_disk_sum", "coll_any", "coll_front", "coll_rear", "coll_side",
                       "coll_disk", "failure_offroad", "failure_collision", "failure_any", "speed", "lon_acc", "lat_acc", "jerk")
 METRICS_SCENE_COLS = 16      # include/cld.h CLD_METRICS_SCENE_COLS
@@ -169,6 +181,9 @@ SIGNATURES = {
     "cld_scene_metrics_state_bytes": (C.c_size_t, [C.c_int32]),
     "cld_scene_metrics_step": (C.c_int, [_P, C.POINTER(CldSceneMetrics), _P, _P, _P, _P, C.c_int32, _P]),
     "cld_scene_metrics_read": (C.c_int, [_P, C.POINTER(CldSceneMetrics), _P, _P, _P, _P]),
+    "cld_occupancy_splat": (C.c_int, [_P, C.POINTER(CldOccupancy), _P, _P, _P, _P]),
+    "cld_occupancy_mark": (C.c_int, [_P, C.POINTER(CldOccupancy), _P, C.c_int32, _P, _P, _P]),
+    "cld_occupancy_read": (C.c_int, [_P, C.POINTER(CldOccupancy), _P, _P, C.c_double, _P, _P, _P, _P, _P]),
     "cld_sort_workspace_bytes": (C.c_size_t, [C.c_int64]),
     "cld_sort_f32": (C.c_int, [_P, _P, _P, C.c_int64, _P, C.c_size_t, _P]),
     "cld_wasserstein_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),

@@ -2142,6 +2142,77 @@ int cld_scene_metrics_read(cld_handle h, const cld_scene_metrics* m, const void*
     return CLD_OK;
 }
 
+/* ---- occupancy coverage and diversity (occupancy_kernels.hip) ---- */
+static_assert(CLD_OCCUPANCY_MAX_WINDOW_CELLS == OCC_MAX_WINDOW_CELLS, "include/cld.h");
+
+static int check_occupancy(cld_handle h, const char* fn, const cld_occupancy* o, OccArgs* a) {
+    const std::string f(fn);
+    if (!o || !o->scene_start || !o->window || !o->cell_start) return fail(h, CLD_ERR_ARG, f + ": null argument");
+    if (o->num_scenes < 1 || o->B_all < 1 || o->B_all > CLD_RASTER_MAX_AGENTS || o->num_scenes > o->B_all || o->cells < 1)
+        return fail(h, CLD_ERR_ARG, f + ": num_scenes / B_all / cells out of range (1 <= num_scenes <= B_all <= CLD_RASTER_MAX_AGENTS, cells >= 1)");
+    if (!std::isfinite(o->offset[0]) || !std::isfinite(o->offset[1])) return fail(h, CLD_ERR_ARG, f + ": offset must be finite");
+    if (!(o->step[0] > 0.0) || !(o->step[1] > 0.0) || !std::isfinite(o->step[0]) || !std::isfinite(o->step[1]))
+        return fail(h, CLD_ERR_ARG, f + ": step must be positive");
+    if (!(o->sigma > 0.0) || !std::isfinite(o->sigma)) return fail(h, CLD_ERR_ARG, f + ": sigma must be positive");
+    if (!(o->kernel_cut > 0.0) || !(o->kernel_cut < 1.0)) return fail(h, CLD_ERR_ARG, f + ": kernel_cut must be inside (0, 1)");
+    // OccupancyGrid.update / get_neighboring_grid_points: radius = sqrt(-2 sigma ln(threshold)), Nx = Ny = int(ceil(radius / xs)) + 1
+    const double half = std::ceil(std::sqrt(-2.0 * o->sigma * std::log(o->kernel_cut)) / o->step[0]) + 1.0;
+    if (!(half >= 1.0) || (2.0 * half + 1.0) * (2.0 * half + 1.0) > (double)OCC_MAX_WINDOW_CELLS)
+        return fail(h, CLD_ERR_ARG, f + ": the kernel window exceeds CLD_OCCUPANCY_MAX_WINDOW_CELLS cells");
+    if (o->n_sem < 1 || o->n_sem > CLD_RASTER_MAX_PLANES || o->drivable_layer < 0 || o->drivable_layer >= o->n_sem)
+        return fail(h, CLD_ERR_ARG, f + ": drivable_layer must be one of the n_sem >= 1 layers");
+    if (o->maps && (!o->scene_map || !o->map_from_world || o->num_maps < 1 || o->map_h < 1 || o->map_w < 1 ||
+                    (int64_t)o->map_h * o->map_w > INT32_MAX))
+        return fail(h, CLD_ERR_ARG, f + ": maps need scene_map, map_from_world, num_maps, map_h and map_w");
+    *a = OccArgs{};
+    a->scene_start = o->scene_start; a->window = o->window; a->cell_start = reinterpret_cast<const long long*>(o->cell_start);
+    a->maps = o->maps; a->scene_map = o->scene_map; a->map_from_world = o->map_from_world;
+    a->cells = o->cells; a->o0 = o->offset[0]; a->o1 = o->offset[1]; a->s0 = o->step[0]; a->s1 = o->step[1]; a->sigma = o->sigma;
+    a->num_scenes = o->num_scenes; a->B_all = o->B_all; a->n_sem = o->n_sem; a->num_maps = o->num_maps; a->map_h = o->map_h;
+    a->map_w = o->map_w; a->layer = o->drivable_layer; a->N = (int)half; a->fill = o->no_map_fill;
+    return CLD_OK;
+}
+
+int cld_occupancy_splat(cld_handle h, const cld_occupancy* o, const float* world, uint64_t* grid, uint64_t* dropped, void* stream) {
+    if (!h) return CLD_ERR_ARG;
+    if (!world || !grid || !dropped) return fail(h, CLD_ERR_ARG, "cld_occupancy_splat: null argument (world, grid or dropped)");
+    OccArgs a;
+    int rc = check_occupancy(h, "cld_occupancy_splat", o, &a);
+    if (rc) return rc;
+    a.world = world; a.grid = reinterpret_cast<unsigned long long*>(grid); a.dropped = reinterpret_cast<unsigned long long*>(dropped);
+    HIPCK(h, launch_occupancy_splat(a, static_cast<hipStream_t>(stream)));
+    return CLD_OK;
+}
+
+int cld_occupancy_mark(cld_handle h, const cld_occupancy* o, const float* world, int32_t n_steps, const uint8_t* ok, uint8_t* success,
+                       void* stream) {
+    if (!h) return CLD_ERR_ARG;
+    if (!world || !ok || !success) return fail(h, CLD_ERR_ARG, "cld_occupancy_mark: null argument (world, ok or success)");
+    OccArgs a;
+    int rc = check_occupancy(h, "cld_occupancy_mark", o, &a);
+    if (rc) return rc;
+    if (n_steps < 1 || (int64_t)n_steps * o->B_all > INT32_MAX) return fail(h, CLD_ERR_ARG, "cld_occupancy_mark: n_steps out of range");
+    a.world = world; a.n_steps = n_steps; a.ok = ok; a.success = success;
+    HIPCK(h, launch_occupancy_mark(a, static_cast<hipStream_t>(stream)));
+    return CLD_OK;
+}
+
+int cld_occupancy_read(cld_handle h, const cld_occupancy* o, const uint64_t* grid, const uint8_t* success, double threshold,
+                       int64_t* counts, double* values, uint8_t* lane, uint64_t* mass, void* stream) {
+    if (!h) return CLD_ERR_ARG;
+    if (!grid) return fail(h, CLD_ERR_ARG, "cld_occupancy_read: null argument (grid)");
+    if (!counts && !values && !lane && !mass) return fail(h, CLD_ERR_ARG, "cld_occupancy_read: no output");
+    if (!(threshold >= 0.0) || !(threshold <= 1048576.0)) return fail(h, CLD_ERR_ARG, "cld_occupancy_read: threshold must be in [0, 2^20]");
+    OccArgs a;
+    int rc = check_occupancy(h, "cld_occupancy_read", o, &a);
+    if (rc) return rc;
+    a.grid_in = reinterpret_cast<const unsigned long long*>(grid); a.success_in = success;
+    a.thr_q = (unsigned long long)std::rint(threshold * 1099511627776.0);
+    a.counts = reinterpret_cast<long long*>(counts); a.values = values; a.lane = lane; a.mass = reinterpret_cast<unsigned long long*>(mass);
+    HIPCK(h, launch_occupancy_read(a, static_cast<hipStream_t>(stream)));
+    return CLD_OK;
+}
+
 /* ---- realism deviation: terms, fp32 sort, Wasserstein-1 (realism_kernels.hip) ---- */
 int32_t cld_debug_sort_items_per_block(void) { return SORT_TILE; }
 

@@ -332,6 +332,38 @@ struct MetricsArgs {
 hipError_t launch_scene_metrics_step(const MetricsArgs& a, hipStream_t s);
 hipError_t launch_scene_metrics_read(const MetricsArgs& a, hipStream_t s);
 
+// the occupancy coverage and diversity metrics (occupancy_kernels.hip; src/tbsim/envs/env_metrics.py:977-1218): one splat launch per
+// environment step adds every agent's kernel window to a fixed-point plane, the mark launch replays an episode's poses into the success
+// plane, the read launch turns planes into counts, values, lane flags and the on-road mass
+constexpr int OCC_MAX_WINDOW_CELLS = 1024;
+struct OccArgs {
+    const float* world;               // [B_all, 3] (splat) or [n_steps, B_all, 3] (mark)
+    const int* scene_start;           // [num_scenes + 1]
+    const int* window;                // [num_scenes, 4] ix0, iy0, nx, ny
+    const long long* cell_start;      // [num_scenes + 1]
+    const float* maps;                // [num_maps, n_sem, map_h, map_w] or null
+    const int* scene_map;             // [num_scenes], < 0: no map (read only when maps != null)
+    const float* map_from_world;      // [num_maps, 3, 3]
+    unsigned long long* grid;         // [cells] (splat)
+    unsigned long long* dropped;      // [num_scenes] (splat)
+    const unsigned char* ok;          // [B_all] (mark)
+    unsigned char* success;           // [cells] (mark)
+    const unsigned long long* grid_in;      // [cells] (read)
+    const unsigned char* success_in;  // [cells] or null (read)
+    long long* counts;                // [num_scenes, 3] or null (read)
+    double* values;                   // [cells] or null (read)
+    unsigned char* lane;              // [cells] or null (read)
+    unsigned long long* mass;         // [num_scenes] or null (read)
+    long long cells;
+    unsigned long long thr_q;         // rint(threshold 2^40) (read)
+    double o0, o1, s0, s1, sigma;
+    int num_scenes, B_all, n_sem, num_maps, map_h, map_w, layer, N, n_steps;
+    float fill;
+};
+hipError_t launch_occupancy_splat(const OccArgs& a, hipStream_t s);
+hipError_t launch_occupancy_mark(const OccArgs& a, hipStream_t s);
+hipError_t launch_occupancy_read(const OccArgs& a, hipStream_t s);
+
 // the realism deviation (realism_kernels.hip; src/trainers/guide_dm_trainer.py:204-295): the compared quantities, an fp32 sort and the
 // Wasserstein-1 distance of two sorted samples.  The sort works on tiles of SORT_TILE keys; its workspace is a second copy of the keys
 // (rounded up to 256 bytes), the digit counts hist[256][tiles] and the 256 digit totals.  The distance leaves one fp64 partial per tile

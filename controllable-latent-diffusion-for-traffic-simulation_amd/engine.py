@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
+import math
 from typing import Mapping, Optional
 
 import numpy as np
@@ -1152,6 +1153,106 @@ class Engine:
             self._check(self.lib.cld_scene_metrics_read(self._h, C.byref(st), _ptr(state), _ptr(per_agent), _ptr(per_scene),
                                                         self._stream()), "cld_scene_metrics_read")
         return per_agent, per_scene
+
+    # ------------------------------------------------------------------ occupancy coverage and diversity (env_metrics.py:977-1218)
+    def occupancy_setup(self, scene_start, window, offset, step=(2.0, 2.0), sigma: float = 1.0, kernel_cut: float = 0.1, maps=None,
+                        scene_map=None, map_from_world=None, drivable_layer: int = 0, no_map_fill: float = -1.0, n_sem: int = 3):
+        """The `cld_occupancy` struct of one grid over a scene set (include/cld.h) -> (struct, B_all, num_scenes, cells, half-width N, the
+        tensors it points to).  window [num_scenes,4] = (ix0, iy0, nx, ny) in cells.  scene_start and the windows are checked here on the
+        host -- the library never validates the contents of device memory -- and cell_start is derived from the windows; everything else
+        is checked by the library."""
+        host = torch.as_tensor(scene_start).to(torch.int64).reshape(-1).cpu()
+        if host.numel() < 2 or int(host[0]) != 0 or bool((host[1:] <= host[:-1]).any()) or int(host[-1]) >= 2 ** 31:
+            raise CldError(f"occupancy: scene_start {host.tolist()} does not split agents into scenes")
+        B_all, S = int(host[-1]), int(host.numel()) - 1
+        ss = host.to(self.device, torch.int32).contiguous()
+        win = torch.as_tensor(window).to(torch.int64).cpu()
+        if tuple(win.shape) != (S, 4):
+            raise CldError(f"occupancy: window must be [{S},4] (ix0, iy0, nx, ny), got {tuple(win.shape)}")
+        if bool((win[:, 2:] < 1).any()) or bool((win.abs() >= 2 ** 30).any()):
+            raise CldError("occupancy: a window needs nx, ny >= 1 and cell indices below 2^30")
+        cs = torch.zeros(S + 1, dtype=torch.int64)
+        cs[1:] = torch.cumsum(win[:, 2] * win[:, 3], 0)
+        cells = int(cs[-1])
+        if cells >= 2 ** 31:
+            raise CldError(f"occupancy: the windows hold {cells} cells (fewer than 2^31)")
+        try:
+            N = int(math.ceil(math.sqrt(-2.0 * float(sigma) * math.log(float(kernel_cut))) / float(step[0]))) + 1
+        except (ValueError, ZeroDivisionError, OverflowError):
+            N = 1                                                    # (the library names what is wrong with sigma, step or kernel_cut)
+        mp = sm = mfw = None
+        num_maps = map_h = map_w = 0
+        if maps is not None:
+            mp = self._f32(maps)
+            if mp.dim() != 4 or mp.shape[1] != n_sem:
+                raise CldError(f"occupancy: maps must be [num_maps,{n_sem},map_h,map_w], got {tuple(mp.shape)}")
+            num_maps, map_h, map_w = int(mp.shape[0]), int(mp.shape[2]), int(mp.shape[3])
+            if scene_map is None or map_from_world is None:
+                raise CldError("occupancy: maps need scene_map and map_from_world")
+            sm = torch.as_tensor(scene_map).to(self.device, torch.int32).contiguous()
+            if tuple(sm.shape) != (S,):
+                raise CldError(f"occupancy: scene_map must be [{S}], got {tuple(sm.shape)}")
+            mfw = self._f32(map_from_world, (num_maps, 3, 3))
+        wd, cd = win.to(self.device, torch.int32).contiguous(), cs.to(self.device).contiguous()
+        dp = lambda t: None if t is None else t.data_ptr()
+        st = _lib.CldOccupancy(ss.data_ptr(), wd.data_ptr(), cd.data_ptr(), dp(mp), dp(sm), dp(mfw), cells,
+                               (C.c_double * 2)(float(offset[0]), float(offset[1])), (C.c_double * 2)(float(step[0]), float(step[1])),
+                               float(sigma), float(kernel_cut), S, B_all, int(n_sem), num_maps, map_h, map_w, int(drivable_layer),
+                               float(no_map_fill))
+        return st, B_all, S, cells, N, (ss, wd, cd, mp, sm, mfw, win, cs)
+
+    def _occupancy_plane(self, setup, t, dtype, what: str, count=None):
+        count = setup[3] if count is None else count
+        if not (isinstance(t, torch.Tensor) and t.device == self.device and t.dtype == dtype and t.is_contiguous() and t.numel() == count):
+            raise CldError(f"occupancy: {what} must be a contiguous {dtype} tensor of {count} elements on {self.device}")
+        return t
+
+    def occupancy_splat(self, setup, world, grid, dropped):
+        """One environment step (cld_occupancy_splat): world [B_all,3] added to the Q40 plane `grid` [cells] (int64 tensor holding the
+        unsigned words) and to `dropped` [num_scenes] (int64), both in place.  No host synchronisation."""
+        world = self._f32(world, (setup[1], 3))
+        grid = self._occupancy_plane(setup, grid, torch.int64, "grid")
+        dropped = self._occupancy_plane(setup, dropped, torch.int64, "dropped", setup[2])
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cld_occupancy_splat(self._h, C.byref(setup[0]), _ptr(world), _ptr(grid), _ptr(dropped), self._stream()),
+                        "cld_occupancy_splat")
+
+    def occupancy_mark(self, setup, world, ok, success):
+        """cld_occupancy_mark: world [n_steps,B_all,3], the poses of one episode; ok [B_all] (non-zero: the agent did not fail);
+        success [cells] uint8, set to 1 in place on every window cell of an ok agent."""
+        world = self._f32(world)
+        if world.dim() != 3 or tuple(world.shape[1:]) != (setup[1], 3) or world.shape[0] < 1:
+            raise CldError(f"occupancy: mark needs world [n_steps >= 1,{setup[1]},3], got {tuple(world.shape)}")
+        ok = torch.as_tensor(ok)
+        ok = ok if (ok.dtype == torch.uint8 and ok.device == self.device) else (ok != 0).to(self.device, torch.uint8)
+        ok = self._occupancy_plane(setup, ok.contiguous(), torch.uint8, "ok", setup[1])
+        success = self._occupancy_plane(setup, success, torch.uint8, "success")
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cld_occupancy_mark(self._h, C.byref(setup[0]), _ptr(world), int(world.shape[0]), _ptr(ok), _ptr(success),
+                                                    self._stream()), "cld_occupancy_mark")
+
+    def occupancy_read(self, setup, grid, success=None, threshold: float = 1e-2, counts: bool = True, values: bool = False,
+                       lane: bool = False, mass: bool = False):
+        """cld_occupancy_read -> dict of the outputs asked for: counts [num_scenes,3] int64 (total, onroad, success), values [cells]
+        float64, lane [cells] uint8, mass [num_scenes] int64 (the Q40 sum of the on-road cells).  No host synchronisation."""
+        S, cells = setup[2], setup[3]
+        grid = self._occupancy_plane(setup, grid, torch.int64, "grid")
+        if success is not None:
+            success = self._occupancy_plane(setup, success, torch.uint8, "success")
+        out = {}
+        if counts:
+            out["counts"] = torch.empty(S, 3, dtype=torch.int64, device=self.device)
+        if values:
+            out["values"] = torch.empty(cells, dtype=torch.float64, device=self.device)
+        if lane:
+            out["lane"] = torch.empty(cells, dtype=torch.uint8, device=self.device)
+        if mass:
+            out["mass"] = torch.empty(S, dtype=torch.int64, device=self.device)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cld_occupancy_read(self._h, C.byref(setup[0]), _ptr(grid), _ptr(success), float(threshold),
+                                                    _ptr(out.get("counts")), _ptr(out.get("values")), _ptr(out.get("lane")),
+                                                    _ptr(out.get("mass")), self._stream()), "cld_occupancy_read")
+        return out
 
     # ------------------------------------------------------------------ realism deviation (guide_dm_trainer.py:204-295)
     def _flat_f32(self, t, what: str) -> torch.Tensor:

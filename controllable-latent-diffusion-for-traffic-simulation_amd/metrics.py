@@ -6,6 +6,11 @@ The arithmetic is `cld_scene_metrics_step` / `cld_scene_metrics_read` (csrc/metr
 quantity).  The bookkeeping here is the state buffer, the step counter and the poses, which move with `cld_world_step` exactly as
 `SceneObserver.advance` moves its own, so the scored poses are the observer's history frames bit for bit.
 
+`OccupancyMetrics` is the registry's other two entries, all_coverage and all_diversity (env_builders.py:43-48: OccupancyCoverage,
+OccupancyDiversity of env_metrics.py:977-1218): Q40 fixed-point occupancy planes filled with integer atomics, one launch per environment
+step and grid (`cld_occupancy_splat` / `cld_occupancy_mark` / `cld_occupancy_read`; csrc/occupancy_kernels.hip).  Only the transport
+problem of the diversity value leaves the device (`emd_linprog`).
+
 `RealismDeviation` is the test stage's other number (src/trainers/guide_dm_trainer.py:204-295): the mean Wasserstein-1 distance between
 ground truth and prediction of three quantities, accumulated and evaluated on the device (`cld_realism_terms`, `cld_sort_f32`,
 `cld_wasserstein_f32`; csrc/realism_kernels.hip).
@@ -99,6 +104,261 @@ class RolloutMetrics:
             "all_failure": {"failure_offroad": s[:, 9], "failure_collision": s[:, 10], "failure_any": s[:, 11]},
             "all_comfort": {"speed": s[:, 12], "lon_acc": s[:, 13], "lat_acc": s[:, 14], "jerk": s[:, 15]},
         }
+
+
+COVERAGE_DEFAULTS = dict(offset=(0.0, 0.0), step=(2.0, 2.0), sigma=1.0, threshold=1e-2)      # env_builders.py:43-45
+DIVERSITY_DEFAULTS = dict(offset=(0.0, 0.0), step=(4.0, 4.0), sigma=1.0)                    # env_builders.py:46-48
+_DEFAULT = object()
+EMD_MAX_CELLS = 1024      # the default transport solver refuses a pair with more cells of mass than this (an LP of EMD_MAX_CELLS^2 flows)
+
+
+def emd_linprog(distr_i, distr_j, distance_matrix):
+    """pyemd.emd's signature on scipy: the cost of the cheapest transport of distr_i onto distr_j under `distance_matrix`, by
+    scipy.optimize.linprog(method="highs") with sparse constraints.  Only cells with mass in either distribution enter (the others carry
+    no flow at the optimum).  scipy is imported here and nowhere else in the package."""
+    import numpy as np
+    try:
+        from scipy.optimize import linprog
+        from scipy.sparse import csr_matrix
+    except ImportError as err:
+        raise CldError("OccupancyMetrics.diversity: the default solver needs scipy (pass solver=, pyemd.emd's signature)") from err
+    p, q, D = np.asarray(distr_i, np.float64), np.asarray(distr_j, np.float64), np.asarray(distance_matrix, np.float64)
+    keep = np.flatnonzero((p > 0) | (q > 0))
+    n = int(keep.size)
+    if n > EMD_MAX_CELLS:
+        raise CldError(f"OccupancyMetrics.diversity: {n} cells carry mass, the default solver takes at most {EMD_MAX_CELLS} (pass solver=)")
+    if n == 0:
+        return 0.0
+    p, q, D = p[keep], q[keep], D[np.ix_(keep, keep)]
+    flow = np.arange(n * n)                                          # flow f[a, b] from cell a of p to cell b of q, row-major
+    A = csr_matrix((np.ones(2 * n * n), (np.concatenate([flow // n, n + flow % n]), np.concatenate([flow, flow]))), shape=(2 * n, n * n))
+    res = linprog(D.reshape(-1), A_eq=A, b_eq=np.concatenate([p, q]), bounds=(0, None), method="highs")
+    if res.status != 0:
+        raise CldError(f"OccupancyMetrics.diversity: linprog did not converge ({res.message})")
+    return float(res.fun)
+
+
+class OccupancyMetrics:
+    """Upstream's two occupancy metrics on the device (src/tbsim/envs/env_metrics.py:977-1218; include/cld.h `cld_occupancy_splat` defines
+    every quantity): `all_coverage` = OccupancyCoverage, one grid over all episodes since `reset()`, and `all_diversity` =
+    OccupancyDiversity, one grid per episode.
+
+    scene_start [num_scenes + 1]; world0 [B_all,3] the world poses the first plans start from; maps / scene_map / map_from_world /
+    drivable_layer / no_map_fill as `RolloutMetrics` takes them; `coverage`: dict(offset, step, sigma, threshold) and `diversity`:
+    dict(offset, step, sigma) over COVERAGE_DEFAULTS / DIVERSITY_DEFAULTS, either may be None (not computed).  A scene's grid is a
+    window of cells: by default the bounding box of its agents in world0 (absent ones left out) +- `reach` metres; `window` =
+    [num_scenes,4] world boxes (x0, y0, x1, y1) instead.  What an agent's kernel window would add outside it is counted by `dropped()`.
+    `max_episodes` bounds the episodes between two `reset()`s (the diversity planes are allocated up front).
+
+    An episode: `begin_episode(world0)`, then `add_step(world)` per environment step or `add_plans(plans_all)` per plan (or pass the
+    object in `metrics=` of `closed_loop_rollout`), then `end_episode(failed)`.  Nothing synchronises before a result is read."""
+
+    def __init__(self, engine, scene_start, world0, maps=None, scene_map=None, map_from_world=None, drivable_layer: int = 0,
+                 coverage=_DEFAULT, diversity=_DEFAULT, reach: float = 100.0, window=None, n_step_action: int = 5, max_episodes: int = 8,
+                 no_map_fill: float = -1.0, n_sem: int = 3):
+        self.engine = engine
+        self.n_step_action = int(n_step_action)
+        if not 1 <= self.n_step_action <= 52:
+            raise CldError(f"OccupancyMetrics: n_step_action = {n_step_action} (1 .. 52)")
+        self.max_episodes = int(max_episodes)
+        if self.max_episodes < 1:
+            raise CldError(f"OccupancyMetrics: max_episodes = {max_episodes} must be at least 1")
+        host = torch.as_tensor(scene_start).to(torch.int64).reshape(-1).cpu()
+        if host.numel() < 2 or int(host[0]) != 0 or bool((host[1:] <= host[:-1]).any()):
+            raise CldError(f"OccupancyMetrics: scene_start {host.tolist()} does not split agents into scenes")
+        self.B_all, self.num_scenes = int(host[-1]), int(host.numel()) - 1
+        self._scene_start = host
+        self._max_agents = int((host[1:] - host[:-1]).max())
+        self.poses = self._world0(world0)
+        boxes = self._boxes(window, float(reach))
+        self._grids = {}
+        for name, cfg, defaults in (("coverage", coverage, COVERAGE_DEFAULTS), ("diversity", diversity, DIVERSITY_DEFAULTS)):
+            if cfg is None:
+                continue
+            cfg = dict(defaults, **({} if cfg is _DEFAULT else cfg))
+            unknown = sorted(set(cfg) - set(defaults))
+            if unknown:
+                raise TypeError(f"OccupancyMetrics: unknown {name} settings {unknown} (one of {sorted(defaults)})")
+            off, step = [float(v) for v in cfg["offset"]], [float(v) for v in cfg["step"]]
+            if not (step[0] > 0.0 and step[1] > 0.0):
+                raise CldError(f"OccupancyMetrics: the {name} grid needs a positive step, got {tuple(cfg['step'])}")
+            lo = torch.floor((boxes[:, :2] - torch.tensor(off, dtype=torch.float64)) / torch.tensor(step, dtype=torch.float64))
+            hi = torch.ceil((boxes[:, 2:] - torch.tensor(off, dtype=torch.float64)) / torch.tensor(step, dtype=torch.float64))
+            if not bool(torch.isfinite(lo).all() and torch.isfinite(hi).all()) or bool((hi - lo >= 2 ** 30).any()):
+                raise CldError(f"OccupancyMetrics: the {name} windows are not finite")
+            win = torch.cat([lo, hi - lo + 1.0], 1).to(torch.int64)
+            setup = engine.occupancy_setup(host, win, off, step, cfg["sigma"], 0.1, maps, scene_map, map_from_world, drivable_layer,
+                                           no_map_fill, n_sem)
+            if (2 * setup[4] + 1) ** 2 > _lib.OCCUPANCY_MAX_WINDOW_CELLS:
+                raise CldError(f"OccupancyMetrics: the {name} kernel window is {2 * setup[4] + 1}^2 cells, above "
+                               f"{_lib.OCCUPANCY_MAX_WINDOW_CELLS} (sigma too large for the step)")
+            planes = self.max_episodes if name == "diversity" else 1
+            self._grids[name] = dict(cfg=cfg, setup=setup, grid=torch.zeros(planes, setup[3], dtype=torch.int64, device=engine.device),
+                                     dropped=torch.zeros(self.num_scenes, dtype=torch.int64, device=engine.device))
+        if "coverage" in self._grids:
+            self._success = torch.zeros(self._grids["coverage"]["setup"][3], dtype=torch.uint8, device=engine.device)
+        self.episodes = 0            # episodes ended since reset()
+        self._open = False
+        self._steps = []             # the open episode's poses, replayed by end_episode
+        self._adds = 0               # steps splatted into the coverage grid since reset()
+
+    def _world0(self, world0):
+        w = torch.as_tensor(world0).to(self.engine.device, torch.float32).contiguous().clone()
+        if tuple(w.shape) != (self.B_all, 3):
+            raise CldError(f"OccupancyMetrics: world0 must be [{self.B_all},3], got {tuple(w.shape)}")
+        return w
+
+    def _boxes(self, window, reach):
+        """-> [num_scenes,4] float64 world boxes (x0, y0, x1, y1) on the host: `window`, or the agents of world0 +- reach."""
+        S = self.num_scenes
+        if window is not None:
+            b = torch.as_tensor(window).to(torch.float64).cpu()
+            if tuple(b.shape) != (S, 4) or not bool(torch.isfinite(b).all()) or bool((b[:, 2:] < b[:, :2]).any()):
+                raise CldError(f"OccupancyMetrics: window must be [{S},4] finite world boxes (x0, y0, x1, y1)")
+            return b
+        if not reach >= 0.0:
+            raise CldError(f"OccupancyMetrics: reach = {reach} must not be negative")
+        xy = self.poses[:, :2].to(torch.float64).cpu()
+        b = torch.zeros(S, 4, dtype=torch.float64)
+        for s in range(S):
+            p = xy[int(self._scene_start[s]):int(self._scene_start[s + 1])]
+            p = p[~torch.isnan(p).any(1)]
+            if p.numel() == 0:
+                raise CldError(f"OccupancyMetrics: scene {s} has no present agent in world0 to place its window around (pass window=)")
+            b[s, :2], b[s, 2:] = p.min(0).values - reach, p.max(0).values + reach
+        return b
+
+    # ---- feeding
+    def reset(self):
+        """Upstream's multi_episode_reset: every plane and counter is emptied (the poses stay)."""
+        for g in self._grids.values():
+            g["grid"].zero_()
+            g["dropped"].zero_()
+        if "coverage" in self._grids:
+            self._success.zero_()
+        self.episodes, self._open, self._steps, self._adds = 0, False, [], 0
+
+    def begin_episode(self, world0=None):
+        """Open the next episode (optionally setting the poses its first plans start from)."""
+        if self._open:
+            raise CldError("OccupancyMetrics.begin_episode: an episode is open (end_episode first)")
+        if self.episodes >= self.max_episodes:
+            raise CldError(f"OccupancyMetrics.begin_episode: max_episodes = {self.max_episodes} episodes have been fed (reset(), or build "
+                           f"with a larger max_episodes)")
+        if world0 is not None:
+            self.poses = self._world0(world0)
+        self._open, self._steps = True, []
+
+    def add_step(self, world):
+        """One environment step: world [B_all,3] (x, y, h), NaN x or y = the agent is absent.  One splat launch per grid, no host
+        synchronisation.  Opens an episode when none is open."""
+        if not self._open:
+            self.begin_episode()
+        if (self._adds + 1) * self._max_agents > 2 ** 24:
+            raise CldError(f"OccupancyMetrics.add_step: {self._adds + 1} steps of a scene of {self._max_agents} agents could add more than "
+                           f"2^24 times into one cell of the Q40 planes (reset() first)")
+        world = self.engine._f32(world, (self.B_all, 3))
+        for name, g in self._grids.items():
+            plane = g["grid"][self.episodes if name == "diversity" else 0]
+            self.engine.occupancy_splat(g["setup"], world, plane, g["dropped"])
+        self._steps.append(world)
+        self._adds += 1
+
+    def add_plans(self, plans_all):
+        """The `n_step_action` executed states of every agent's plan [B_all,52,6], taken to the world exactly as
+        `RolloutMetrics.add_plans` takes them, each fed as one environment step; the poses move to the last of them."""
+        plans = torch.as_tensor(plans_all).to(self.engine.device, torch.float32).contiguous()
+        if tuple(plans.shape) != (self.B_all, 52, 6):
+            raise CldError(f"OccupancyMetrics: plans must cover all {self.B_all} agents as [{self.B_all},52,6], got {tuple(plans.shape)}")
+        centroid, yaw = self.poses[:, :2].contiguous(), self.poses[:, 2].contiguous()
+        world = None
+        for k in range(self.n_step_action):
+            world = self.engine.world_step(plans, centroid, yaw, k)[0]
+            self.add_step(world)
+        self.poses = world
+
+    def end_episode(self, failed):
+        """Close the episode: failed [B_all] (non-zero: the agent failed in this episode, e.g. `rm.per_agent()[:, 11] != 0` of a
+        `RolloutMetrics`).  The episode's poses are replayed once into the success plane (cld_occupancy_mark)."""
+        if not self._open:
+            raise CldError("OccupancyMetrics.end_episode: no episode is open")
+        failed = torch.as_tensor(failed).to(self.engine.device).reshape(-1)
+        if failed.numel() != self.B_all:
+            raise CldError(f"OccupancyMetrics.end_episode: failed must be [{self.B_all}], got {failed.numel()} values")
+        if "coverage" in self._grids and self._steps:
+            self.engine.occupancy_mark(self._grids["coverage"]["setup"], torch.stack(self._steps), (failed == 0).to(torch.uint8),
+                                       self._success)
+        self.episodes += 1
+        self._open, self._steps = False, []
+
+    # ---- results
+    def _grid(self, name: str, what: str):
+        if name not in self._grids:
+            raise CldError(f"OccupancyMetrics.{what}: built with {name}=None")
+        if self._open:
+            raise CldError(f"OccupancyMetrics.{what}: an episode is open (end_episode first)")
+        return self._grids[name]
+
+    def coverage(self):
+        """OccupancyCoverage.summarize_grid over every episode since reset() -> {"total", "onroad", "success"}: int64 [num_scenes]
+        device tensors."""
+        g = self._grid("coverage", "coverage")
+        c = self.engine.occupancy_read(g["setup"], g["grid"][0], self._success, threshold=g["cfg"]["threshold"])["counts"]
+        return {"total": c[:, 0], "onroad": c[:, 1], "success": c[:, 2]}
+
+    def dropped(self, grid: str = "coverage"):
+        """-> [num_scenes] int64: the kernel-window cells that fell outside the scene's window since reset(), of grid "coverage" or
+        "diversity".  Non-zero: the counts miss cells; build with a larger `reach` or `window`."""
+        if grid not in self._grids:
+            raise CldError(f"OccupancyMetrics.dropped: built with {grid}=None")
+        return self._grids[grid]["dropped"]
+
+    def cell_points(self, grid: str, scene: int):
+        """-> [nx ny, 2] float64 device tensor: the world points of the cells of `scene`'s window, in the planes' order."""
+        g = self._grids[grid]
+        ix0, iy0, nx, ny = (int(v) for v in g["setup"][5][6][scene])
+        dev = self.engine.device
+        off, step = g["cfg"]["offset"], g["cfg"]["step"]
+        gx = torch.arange(ix0, ix0 + nx, dtype=torch.float64, device=dev) * float(step[0]) + float(off[0])
+        gy = torch.arange(iy0, iy0 + ny, dtype=torch.float64, device=dev) * float(step[1]) + float(off[1])
+        return torch.stack([gx[:, None].expand(nx, ny), gy[None, :].expand(nx, ny)], -1).reshape(nx * ny, 2)
+
+    def diversity_distributions(self):
+        """-> per scene (points [n,2], distr [episodes,n]) float64 on the device: the world points of the scene's window cells and, per
+        episode, OccupancyDiversity's distribution values lane / sum over them (a row without on-road mass is NaN).  Cells outside
+        upstream's union of touched cells hold 0."""
+        g = self._grid("diversity", "diversity_distributions")
+        setup, E = g["setup"], self.episodes
+        cs = g["setup"][5][7]
+        rows = []
+        for e in range(E):
+            r = self.engine.occupancy_read(setup, g["grid"][e], counts=False, values=True, lane=True, mass=True)
+            rows.append((r["values"] * r["lane"].to(torch.float64), r["mass"].to(torch.float64) / _lib.OCCUPANCY_Q))
+        out = []
+        for s in range(self.num_scenes):
+            a, b = int(cs[s]), int(cs[s + 1])
+            distr = torch.stack([v[a:b] / m[s] for v, m in rows]) if E else torch.zeros(0, b - a, dtype=torch.float64,
+                                                                                      device=self.engine.device)
+            out.append((self.cell_points("diversity", s), distr))
+        return out
+
+    def diversity(self, solver=None):
+        """OccupancyDiversity.get_multi_episode_metrics -> [num_scenes] float64 (host): per scene the mean over episode pairs of the
+        earth mover's distance of their distributions, ground distance Euclidean between cell points.  The transport problem is a
+        linear programme and is solved on the host: `solver(distr_i, distr_j, distance_matrix)` with pyemd.emd's signature, default
+        `emd_linprog`.  Fewer than two episodes, or an episode without on-road mass, give NaN, as upstream's arithmetic does."""
+        import numpy as np
+        solver = emd_linprog if solver is None else solver
+        res = np.full(self.num_scenes, np.nan)
+        for s, (pts, distr) in enumerate(self.diversity_distributions()):
+            d = distr.cpu().numpy()
+            if d.shape[0] < 2 or np.isnan(d).any():
+                continue
+            keep = np.flatnonzero((d > 0).any(0))                   # (cells without mass in any episode carry no flow)
+            p, d = pts.cpu().numpy()[keep], d[:, keep]
+            D = np.linalg.norm(p[:, None] - p[None], axis=2)
+            res[s] = np.mean([solver(d[i], d[j], D) for i in range(d.shape[0]) for j in range(i)])
+        return torch.from_numpy(res)
 
 
 class RealismDeviation:

@@ -397,7 +397,8 @@ def closed_loop_rollout(policy: CldPolicy, cond_fn: Callable, centroid, yaw, cur
     The world moves on the EXECUTED trajectory (the selected sample, stationary agents held in place).
     `metrics` (`cld_amd.metrics.RolloutMetrics`): after the environment step of each sim step the `n_step_action` executed states of every
     agent are scored on the device (`metrics.add_plans` on what `gather` returned, or on this rank's trajectories without `gather`;
-    that tensor must cover the B_all agents of `metrics`); without it the loop is exactly what it was.
+    that tensor must cover the B_all agents of `metrics`); without it the loop is exactly what it was.  A tuple or list of scorers
+    (anything with `B_all` and `add_plans`, e.g. a `RolloutMetrics` and a `cld_amd.metrics.OccupancyMetrics`) is fed in its order.
     With a goal loss configured (`global_target_pos`, `global_target_pos_at_time`) the observation must tell get_action where the
     agents are and where they have been; the fields `cond_fn`'s observation lacks are filled in here: `world_from_agent` /
     `agent_from_world` [B,3,3] from the current world pose, and `agent_hist` [B,n_step_action,2]: the `n_step_action` executed states
@@ -417,8 +418,9 @@ def closed_loop_rollout(policy: CldPolicy, cond_fn: Callable, centroid, yaw, cur
         four = len(inspect.signature(cond_fn).parameters) >= 4
     except (TypeError, ValueError):
         four = False
+    scorers = () if metrics is None else tuple(metrics) if isinstance(metrics, (tuple, list)) else (metrics,)
     poses, plans = [], None
-    hist_world = None                                 # executed states of the previous plan, world frame [B,n_step_action,2]
+    hist_world = None                             # executed states of the previous plan, world frame [B,n_step_action,2]
     for step in range(n_sim_steps):
         with tm("step"):
             with tm("obs"):
@@ -456,12 +458,12 @@ def closed_loop_rollout(policy: CldPolicy, cond_fn: Callable, centroid, yaw, cur
                 if has_goal:
                     hist_world = transform_points(traj[:, :n_step_action, :2], frames_from_pose(world))
                 world, cs = eng.world_step(traj, world[:, :2].contiguous(), world[:, 2].contiguous(), n_step_action - 1)
-                if metrics is not None:
+                for scorer in scorers:
                     scored = plans if gather is not None else traj
-                    if tuple(scored.shape) != (metrics.B_all, 52, 6):
-                        raise CldError(f"closed_loop_rollout: metrics= scores all {metrics.B_all} agents, the executed plans are "
+                    if tuple(scored.shape) != (scorer.B_all, 52, 6):
+                        raise CldError(f"closed_loop_rollout: metrics= scores all {scorer.B_all} agents, the executed plans are "
                                        f"{tuple(scored.shape)} (pass gather= so that every rank's plans are there)")
-                    metrics.add_plans(scored)
+                    scorer.add_plans(scored)
         poses.append(world)
     return torch.stack(poses)
 

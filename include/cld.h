@@ -581,6 +581,84 @@ int cld_scene_metrics_read(cld_handle h, const cld_scene_metrics* m, const void*
                            float* per_agent /*[B_all, CLD_METRICS_AGENT_COLS] or NULL*/,
                            float* per_scene /*[num_scenes, CLD_METRICS_SCENE_COLS] or NULL*/, void* stream);
 
+/* The occupancy metrics of a closed-loop evaluation, kept on the device: what upstream registers as all_coverage = OccupancyCoverage (grid
+ * step 2 m) and all_diversity = OccupancyDiversity (grid step 4 m) (src/tbsim/evaluation/env_builders.py:35-52; the classes and their
+ * OccupancyGrid: src/tbsim/envs/env_metrics.py:977-1218).  Needs no weights; plain fp64 / integers in both library precisions; none of the
+ * three calls synchronises.  All pointers are DEVICE.
+ *
+ * The grid.  Cell (i, j) of a grid with offset (o0, o1) and step (s0, s1) is the world point g = (s0 i + o0, s1 j + o1).  Scene s owns the
+ * cells of its window, i in [ix0, ix0 + nx), j in [iy0, iy0 + ny) (window[s] = ix0, iy0, nx, ny), stored row-major [nx, ny] from
+ * cell_start[s] in every plane; a plane has `cells` = cell_start[num_scenes] elements.
+ *
+ * cld_occupancy_splat is one environment step over all B_all agents of all scenes: world [B_all,3] (x, y, h).  Agent a is VALID when
+ * neither x nor y is NaN.  A valid agent at p = (x, y):
+ *   centre cell   c = (rint((x - o0) / s0), rint((y - o1) / s1)) in fp64, half to even (np.round);
+ *   half-width    N = ceil(sqrt(-2 sigma ln(kernel_cut)) / s0) + 1 for BOTH axes (upstream divides by the x step twice);
+ *   every cell c + d, d in [-N, N]^2 -- no cut-off inside the window: 7 x 7 cells at sigma 1 / step 2, 5 x 5 at step 4, 9 x 9 at sigma 4 /
+ *   step 2 -- receives k = exp(-|p - g|^2 / 2 / sigma) in fp64 (the divisor is sigma, not sigma^2, as upstream's is), added to grid[cell] as
+ *   the unsigned 64-bit integer rint(k 2^40) with one ordinary vector integer atomic add.
+ * grid is therefore Q40 fixed point: each add rounds by at most 2^-41, and integer adds commute, so the plane holds the same bits on every
+ * run and under every permutation of agents and order of steps.  A cell of the agent's window outside the scene's window is not written;
+ * it adds 1 to dropped[s] (unsigned 64-bit, one atomic add per agent).  The caller keeps the adds into one cell below 2^24 (each is at most
+ * 2^40), or the sum wraps.
+ *
+ * cld_occupancy_mark replays the poses of one episode, world [n_steps, B_all, 3], once its failures are known: every cell of the window of
+ * every valid pose of an agent with ok[a] != 0 that lies in the scene's window gets success[cell] = 1 (idempotent byte stores; other bytes
+ * are left as they are).  After every episode has been marked, success[cell] = 1 exactly where upstream's per-cell set of (episode, agent)
+ * pairs holds a pair that did not fail.
+ *
+ * cld_occupancy_read, any of the outputs (at least one; the others NULL):
+ *   counts [num_scenes, 3] int64: total = #(grid > T), onroad = #(lane and grid > T), success = #(lane and success and grid > T) over the
+ *                  scene's window, T = rint(threshold 2^40) compared on the integers (OccupancyCoverage.summarize_grid with v > threshold,
+ *                  v lane > threshold, v lane ok > threshold; lane and ok are 0 / 1).  success == NULL counts no cell as a success.
+ *   values [cells] fp64 = grid / 2^40 (exact below 2^53);  lane [cells] uint8;
+ *   mass [num_scenes] uint64 = the sum of grid over the scene's on-road cells, exact: OccupancyDiversity's distribution of one episode is
+ *                  values lane / (mass / 2^40).
+ * lane(cell) is defined by this project: the drivable value of the map at the cell's world point g under the rule of drv in
+ * cld_scene_metrics above -- g rounded to fp32, map pixel rint(map_from_world . g) of layer `drivable_layer`, value != 0; outside the map,
+ * with scene_map[s] < 0 (or >= num_maps) and with maps == NULL it is no_map_fill != 0 -- evaluated by the same device function.  It is a
+ * function of the cell alone and is evaluated at read time.
+ *
+ * Differences from upstream, on purpose:
+ *   absent agents   contribute nothing.  Upstream maps NaN coordinates to cell (0, 0) and adds NaN there, which removes the cells around the
+ *                   grid origin from every count.
+ *   lane flag       from the map at the cell's point, not from the raster of the last agent that wrote the cell (upstream truncates the
+ *                   point's raster coordinates in that agent's raster and keeps the last writer's answer).  The two agree wherever the cell
+ *                   point is not within raster rounding (about 1 m at 2 px / m) of a drivable boundary.
+ *   bounded window  a scene's grid is its window, with the dropped counter, not an unbounded dict.
+ *   fixed point     values are Q40: a cell differs from upstream's fp64 sum by at most (adds into the cell) 2^-41 plus fp64 rounding.
+ *   diversity       is evaluated by the caller from values, lane and mass (a transport problem; the Python layer solves it on the host);
+ *                   fewer than two episodes or an episode without on-road mass give NaN, as upstream's arithmetic does.
+ *
+ * CLD_ERR_ARG (nothing is skipped silently): NULL o / world / grid / dropped / ok / success (mark) / scene_start / window / cell_start,
+ * num_scenes or B_all < 1, num_scenes > B_all, cells < 1, step <= 0, sigma <= 0, kernel_cut outside (0, 1), a window of more than
+ * CLD_OCCUPANCY_MAX_WINDOW_CELLS = (2 N + 1)^2 cells, non-finite offset / step / sigma, maps without their companions, drivable_layer
+ * outside [0, n_sem) (n_sem >= 1 even without maps), n_steps < 1 or n_steps B_all >= 2^31 (mark), a threshold outside [0, 2^20] or no
+ * output (read).  The CONTENTS of scene_start, window and cell_start are never validated by the library (device memory; the Python layer
+ * checks them on the host): the caller guarantees the split of cld_scene_metrics, nx, ny >= 1 and cell_start[s + 1] = cell_start[s] + nx
+ * ny from 0 to `cells`.  The kernels clamp what they read, and no index outside [0, cells) is ever touched. */
+#define CLD_OCCUPANCY_MAX_WINDOW_CELLS 1024
+typedef struct cld_occupancy {
+    const int32_t* scene_start;     /* DEVICE [num_scenes + 1] */
+    const int32_t* window;          /* DEVICE [num_scenes, 4] ix0, iy0, nx, ny */
+    const int64_t* cell_start;      /* DEVICE [num_scenes + 1] flat offsets into the cell planes */
+    const float*   maps;            /* DEVICE [num_maps, n_sem, map_h, map_w] or NULL */
+    const int32_t* scene_map;       /* DEVICE [num_scenes], < 0: no map */
+    const float*   map_from_world;  /* DEVICE [num_maps, 3, 3] */
+    int64_t cells;                  /* the length of every cell plane */
+    double  offset[2], step[2], sigma, kernel_cut;      /* kernel_cut: upstream's 0.1 */
+    int32_t num_scenes, B_all, n_sem, num_maps, map_h, map_w, drivable_layer;
+    float   no_map_fill;
+} cld_occupancy;
+
+int cld_occupancy_splat(cld_handle h, const cld_occupancy* o, const float* world /*[B_all,3]*/, uint64_t* grid /*[cells]*/,
+                        uint64_t* dropped /*[num_scenes]*/, void* stream);
+int cld_occupancy_mark(cld_handle h, const cld_occupancy* o, const float* world /*[n_steps,B_all,3]*/, int32_t n_steps,
+                       const uint8_t* ok /*[B_all]*/, uint8_t* success /*[cells]*/, void* stream);
+int cld_occupancy_read(cld_handle h, const cld_occupancy* o, const uint64_t* grid /*[cells]*/, const uint8_t* success /*[cells] or NULL*/,
+                       double threshold, int64_t* counts /*[num_scenes,3] or NULL*/, double* values /*[cells] or NULL*/,
+                       uint8_t* lane /*[cells] or NULL*/, uint64_t* mass /*[num_scenes] or NULL*/, void* stream);
+
 /* The realism deviation of the test stage (src/trainers/guide_dm_trainer.py:204-295): the mean of three Wasserstein-1 distances between
  * ground-truth and predicted samples of the longitudinal acceleration, the lateral acceleration and the jerk.  Three primitives; none
  * needs weights, none depends on the handle's precision mode (plain fp32 / fp64 in both), none synchronises.  All pointers are DEVICE.
