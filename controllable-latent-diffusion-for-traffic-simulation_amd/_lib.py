@@ -119,6 +119,25 @@ class CldSceneMetrics(C.Structure):
                 ("px_per_m", C.c_float), ("ego_center", C.c_float * 2), ("no_map_fill", C.c_float)]
 
 
+class CldGuideMetrics(C.Structure):
+    """include/cld.h `cld_guide_metrics` (the scene set and the entry table the guidance satisfaction metrics are computed over, device
+    pointers)."""
+    _fields_ = [("extent", C.c_void_p), ("scene_start", C.c_void_p), ("maps", C.c_void_p), ("scene_map", C.c_void_p),
+                ("map_from_world", C.c_void_p), ("entry_kind", C.c_void_p), ("entry_scene", C.c_void_p), ("member_start", C.c_void_p),
+                ("members", C.c_void_p), ("excl_start", C.c_void_p), ("excluded", C.c_void_p), ("param_start", C.c_void_p),
+                ("params", C.c_void_p),
+                ("num_entries", C.c_int32), ("num_members", C.c_int32), ("num_excluded", C.c_int32), ("num_params", C.c_int32),
+                ("num_scenes", C.c_int32), ("B_all", C.c_int32), ("n_sem", C.c_int32), ("height", C.c_int32), ("width", C.c_int32),
+                ("num_maps", C.c_int32), ("map_h", C.c_int32), ("map_w", C.c_int32), ("drivable_layer", C.c_int32),
+                ("px_per_m", C.c_float), ("ego_center", C.c_float * 2), ("no_map_fill", C.c_float)]
+
+
+# cld_guide_metrics.entry_kind (include/cld.h CLD_GM_*), under upstream's metric names
+GUIDE_METRIC_KINDS = {"target_speed": 0, "speed_limit": 1, "acc_limit": 2, "agent_collision": 3, "agent_collision_disk": 4, "social_dist": 5,
+                      "map_collision": 6, "map_collision_disk": 7, "target_pos": 8, "global_target_pos": 9, "target_pos_at_time": 10,
+                      "global_target_pos_at_time": 11, "social_group": 12}
+
+
 class CldOccupancy(C.Structure):
     """include/cld.h `cld_occupancy` (one occupancy grid over a scene set: windows, cell offsets, map and kernel settings, device pointers)."""
     _fields_ = [("scene_start", C.c_void_p), ("window", C.c_void_p), ("cell_start", C.c_void_p), ("maps", C.c_void_p),
@@ -181,6 +200,9 @@ SIGNATURES = {
     "cld_scene_metrics_state_bytes": (C.c_size_t, [C.c_int32]),
     "cld_scene_metrics_step": (C.c_int, [_P, C.POINTER(CldSceneMetrics), _P, _P, _P, _P, C.c_int32, _P]),
     "cld_scene_metrics_read": (C.c_int, [_P, C.POINTER(CldSceneMetrics), _P, _P, _P, _P]),
+    "cld_guide_metrics_state_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "cld_guide_metrics_step": (C.c_int, [_P, C.POINTER(CldGuideMetrics), _P, _P, _P, _P, C.c_int32, _P]),
+    "cld_guide_metrics_read": (C.c_int, [_P, C.POINTER(CldGuideMetrics), _P, _P, _P, _P]),
     "cld_occupancy_splat": (C.c_int, [_P, C.POINTER(CldOccupancy), _P, _P, _P, _P]),
     "cld_occupancy_mark": (C.c_int, [_P, C.POINTER(CldOccupancy), _P, C.c_int32, _P, _P, _P]),
     "cld_occupancy_read": (C.c_int, [_P, C.POINTER(CldOccupancy), _P, _P, C.c_double, _P, _P, _P, _P, _P]),

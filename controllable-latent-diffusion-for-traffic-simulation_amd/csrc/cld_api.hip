@@ -2142,6 +2142,70 @@ int cld_scene_metrics_read(cld_handle h, const cld_scene_metrics* m, const void*
     return CLD_OK;
 }
 
+/* ---- guidance satisfaction metrics (guide_metrics_kernels.hip) ---- */
+size_t cld_guide_metrics_state_bytes(int32_t num_entries, int32_t num_members) {
+    if (num_entries < 1 || num_members < 1) return 0;
+    return (size_t)num_entries * GUIDE_METRICS_ENTRY_BYTES + (size_t)num_members * GUIDE_METRICS_MEMBER_BYTES;
+}
+
+static int check_guide_metrics(cld_handle h, const char* fn, const cld_guide_metrics* m, const void* state, GuideMetricsArgs* a) {
+    const std::string f(fn);
+    if (!m || !state || !m->extent || !m->scene_start || !m->entry_kind || !m->entry_scene || !m->member_start || !m->members ||
+        !m->excl_start || !m->param_start)
+        return fail(h, CLD_ERR_ARG, f + ": null argument");
+    if (reinterpret_cast<uintptr_t>(state) % 16) return fail(h, CLD_ERR_ARG, f + ": state must be 16-byte aligned");
+    if (m->num_scenes < 1 || m->B_all < 1 || m->B_all > CLD_RASTER_MAX_AGENTS || m->num_scenes > m->B_all)
+        return fail(h, CLD_ERR_ARG, f + ": num_scenes / B_all out of range (1 <= num_scenes <= B_all <= CLD_RASTER_MAX_AGENTS)");
+    if (m->num_entries < 1 || m->num_members < 1 || m->num_members > CLD_RASTER_MAX_AGENTS || m->num_entries > CLD_RASTER_MAX_AGENTS)
+        return fail(h, CLD_ERR_ARG, f + ": num_entries / num_members out of range (1 .. CLD_RASTER_MAX_AGENTS)");
+    if (m->num_excluded < 0 || (m->num_excluded > 0 && !m->excluded) || m->num_params < 0 || (m->num_params > 0 && !m->params))
+        return fail(h, CLD_ERR_ARG, f + ": num_excluded / num_params need their arrays");
+    if (m->height < 1 || m->width < 1 || (int64_t)m->height * m->width > CLD_RASTER_MAX_PIXELS)
+        return fail(h, CLD_ERR_ARG, f + ": height x width out of range (include/cld.h CLD_RASTER_MAX_PIXELS)");
+    if (!(m->px_per_m > 0.f)) return fail(h, CLD_ERR_ARG, f + ": px_per_m must be positive");
+    if (m->n_sem < 1 || m->n_sem > CLD_RASTER_MAX_PLANES || m->drivable_layer < 0 || m->drivable_layer >= m->n_sem)
+        return fail(h, CLD_ERR_ARG, f + ": drivable_layer must be one of the n_sem >= 1 layers");
+    if (m->maps && (!m->scene_map || !m->map_from_world || m->num_maps < 1 || m->map_h < 1 || m->map_w < 1 ||
+                    (int64_t)m->map_h * m->map_w > INT32_MAX))
+        return fail(h, CLD_ERR_ARG, f + ": maps need scene_map, map_from_world, num_maps, map_h and map_w");
+    *a = GuideMetricsArgs{};
+    a->extent = m->extent; a->scene_start = m->scene_start; a->maps = m->maps; a->scene_map = m->scene_map;
+    a->map_from_world = m->map_from_world; a->entry_kind = m->entry_kind; a->entry_scene = m->entry_scene;
+    a->member_start = m->member_start; a->members = m->members; a->excl_start = m->excl_start;
+    a->excluded = m->num_excluded > 0 ? m->excluded : nullptr; a->param_start = m->param_start;
+    a->params = m->num_params > 0 ? m->params : nullptr; a->state = const_cast<void*>(state);
+    a->num_entries = m->num_entries; a->num_members = m->num_members; a->num_excluded = m->num_excluded; a->num_params = m->num_params;
+    a->num_scenes = m->num_scenes; a->B_all = m->B_all; a->n_sem = m->n_sem; a->num_maps = m->num_maps; a->map_h = m->map_h;
+    a->map_w = m->map_w; a->H = m->height; a->W = m->width; a->layer = m->drivable_layer;
+    a->ppm = m->px_per_m; a->ox = (1.f + m->ego_center[0]) * 0.5f * (float)m->width; a->oy = (1.f + m->ego_center[1]) * 0.5f * (float)m->height;
+    a->fill = m->no_map_fill;
+    return CLD_OK;
+}
+
+int cld_guide_metrics_step(cld_handle h, const cld_guide_metrics* m, const float* world, const float* speed, const float* acc, void* state,
+                           int32_t global_t, void* stream) {
+    if (!h) return CLD_ERR_ARG;
+    if (!world || !speed || !acc) return fail(h, CLD_ERR_ARG, "cld_guide_metrics_step: null argument (world / speed / acc)");
+    if (global_t < 0) return fail(h, CLD_ERR_ARG, "cld_guide_metrics_step: global_t < 0");
+    GuideMetricsArgs a;
+    int rc = check_guide_metrics(h, "cld_guide_metrics_step", m, state, &a);
+    if (rc) return rc;
+    a.world = world; a.speed = speed; a.acc = acc; a.global_t = global_t;
+    HIPCK(h, launch_guide_metrics_step(a, static_cast<hipStream_t>(stream)));
+    return CLD_OK;
+}
+
+int cld_guide_metrics_read(cld_handle h, const cld_guide_metrics* m, const void* state, double* per_entry, double* per_member, void* stream) {
+    if (!h) return CLD_ERR_ARG;
+    if (!per_entry && !per_member) return fail(h, CLD_ERR_ARG, "cld_guide_metrics_read: no output");
+    GuideMetricsArgs a;
+    int rc = check_guide_metrics(h, "cld_guide_metrics_read", m, state, &a);
+    if (rc) return rc;
+    a.per_entry = per_entry; a.per_member = per_member;
+    HIPCK(h, launch_guide_metrics_read(a, static_cast<hipStream_t>(stream)));
+    return CLD_OK;
+}
+
 /* ---- occupancy coverage and diversity (occupancy_kernels.hip) ---- */
 static_assert(CLD_OCCUPANCY_MAX_WINDOW_CELLS == OCC_MAX_WINDOW_CELLS, "include/cld.h");
 

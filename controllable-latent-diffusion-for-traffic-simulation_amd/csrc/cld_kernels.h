@@ -332,6 +332,37 @@ struct MetricsArgs {
 hipError_t launch_scene_metrics_step(const MetricsArgs& a, hipStream_t s);
 hipError_t launch_scene_metrics_read(const MetricsArgs& a, hipStream_t s);
 
+// the guidance satisfaction metrics (guide_metrics_kernels.hip; src/tbsim/utils/guidance_metrics.py): one step launch per environment step
+// over every entry of every scene updates one row per entry and one per (entry, member); the read launch finalises them.  The raster and
+// map fields are named as MetricsArgs names them (metrics_device.h)
+constexpr int GUIDE_METRICS_ENTRY_BYTES = 32, GUIDE_METRICS_MEMBER_BYTES = 80;
+struct GuideMetricsArgs {
+    const float* world;               // [B_all, 3] (step launch)
+    const float* speed;               // [B_all] (step launch)
+    const float* acc;                 // [B_all] (step launch)
+    const float* extent;              // [B_all, 3]
+    const int* scene_start;           // [num_scenes + 1]
+    const float* maps;                // [num_maps, n_sem, map_h, map_w] or null
+    const int* scene_map;             // [num_scenes]
+    const float* map_from_world;      // [num_maps, 3, 3]
+    const int* entry_kind;            // [E]
+    const int* entry_scene;           // [E]
+    const int* member_start;          // [E + 1]
+    const int* members;               // [num_members]
+    const int* excl_start;            // [E + 1]
+    const int* excluded;              // [num_excluded] or null
+    const int* param_start;           // [E + 1]
+    const double* params;             // [num_params] or null
+    void* state;                      // [E] entry rows, then [num_members] member rows
+    double* per_entry;                // [E] or null (read launch)
+    double* per_member;               // [num_members] or null (read launch)
+    int num_entries, num_members, num_excluded, num_params;
+    int num_scenes, B_all, n_sem, num_maps, map_h, map_w, H, W, layer, global_t;
+    float ppm, ox, oy, fill;
+};
+hipError_t launch_guide_metrics_step(const GuideMetricsArgs& a, hipStream_t s);
+hipError_t launch_guide_metrics_read(const GuideMetricsArgs& a, hipStream_t s);
+
 // the occupancy coverage and diversity metrics (occupancy_kernels.hip; src/tbsim/envs/env_metrics.py:977-1218): one splat launch per
 // environment step adds every agent's kernel window to a fixed-point plane, the mark launch replays an episode's poses into the success
 // plane, the read launch turns planes into counts, values, lane flags and the on-road mass

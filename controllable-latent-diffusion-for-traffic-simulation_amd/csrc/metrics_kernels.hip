@@ -11,6 +11,7 @@
 // every run.  scene_metrics_read_kernel, one workgroup per scene, finalises the rows and sums them in a fixed order (fp64 partials per
 // thread, a fixed LDS tree).  Plain fp32 in both library precisions.
 #include "cld_kernels.h"
+#include "metrics_device.h"
 
 namespace cld {
 
@@ -32,16 +33,6 @@ struct MetricsRow {
     unsigned int reserved[2];
 };
 static_assert(sizeof(MetricsRow) == METRICS_ROW_BYTES, "cld_scene_metrics_state_bytes");
-
-// cos, sin of linspace(0, 2 pi, 13), formed in double (both ends kept, as upstream's batch_detect_off_road_disk does)
-__device__ const float kDiskCos[13] = {(float)1.0, (float)0.8660254037844387, (float)0.5000000000000001, (float)6.123233995736766e-17,
-                                       (float)-0.4999999999999998, (float)-0.8660254037844387, (float)-1.0, (float)-0.8660254037844386,
-                                       (float)-0.5000000000000004, (float)-1.8369701987210297e-16, (float)0.5000000000000001,
-                                       (float)0.8660254037844384, (float)1.0};
-__device__ const float kDiskSin[13] = {(float)0.0, (float)0.49999999999999994, (float)0.8660254037844386, (float)1.0,
-                                       (float)0.8660254037844387, (float)0.49999999999999994, (float)1.2246467991473532e-16,
-                                       (float)-0.5000000000000001, (float)-0.8660254037844384, (float)-1.0, (float)-0.8660254037844386,
-                                       (float)-0.5000000000000004, (float)-2.4492935982947064e-16};
 
 // the length of the segment (x0, y0) -> (x1, y1), of length `len`, inside the box |x| <= b0, |y| <= b1 (Liang-Barsky)
 __device__ inline float clipped_length(float x0, float y0, float x1, float y1, float len, float b0, float b1) {
@@ -74,36 +65,14 @@ __global__ __launch_bounds__(kWaves * 64) void scene_metrics_step_kernel(const M
     const float ri = 0.5f * fminf(p.extent[(size_t)i * 3], p.extent[(size_t)i * 3 + 1]);
     const bool valid = !(isnan(xi) || isnan(yi));
     const float c = cosf(hi_), s = sinf(hi_);
-    int sc = 0, hi = p.num_scenes;                               // scene_start[sc] <= i < scene_start[sc + 1]
-    while (hi - sc > 1) {
-        const int mid = (sc + hi) >> 1;
-        if (p.scene_start[mid] <= i) sc = mid; else hi = mid;
-    }
+    const int sc = mdev::scene_of(p.scene_start, p.num_scenes, i);
 
     // ---- off road: lane 52 the centroid pixel, lanes 0 .. 51 the disk samples (radius index major, as upstream reshapes them)
     unsigned int off = 0u, dsk = 0u;
     if (valid) {
         float fu = p.ox, fv = p.oy;
-        if (lane < 52) {
-            const int k = lane / 13, a = lane - k * 13;
-            const float rad = p.ppm * ri * (0.25f * (float)(k + 1));
-            fu = fminf(fmaxf(p.ox + rad * kDiskCos[a], 0.f), (float)(p.W - 1));
-            fv = fminf(fmaxf(p.oy + rad * kDiskSin[a], 0.f), (float)(p.H - 1));
-        }
-        const int u = (int)fminf(fmaxf(rintf(fu), 0.f), (float)(p.W - 1)), v = (int)fminf(fmaxf(rintf(fv), 0.f), (float)(p.H - 1));
-        int m = p.maps ? p.scene_map[sc] : -1;
-        if (m >= p.num_maps) m = -1;
-        float x = p.fill;
-        if (m >= 0) {                                            // raster_kernel's semantic plane, for this one pixel
-            const float* M = p.map_from_world + (size_t)m * 9;
-            const float inv_ppm = 1.f / p.ppm;
-            const float ay = ((float)v - p.oy) * inv_ppm;
-            const float ax = ((float)u - p.ox) * inv_ppm;
-            const float wx = xi + (c * ax - s * ay), wy = yi + (s * ax + c * ay);
-            const float mx = rintf(M[0] * wx + M[1] * wy + M[2]), my = rintf(M[3] * wx + M[4] * wy + M[5]);
-            if (mx >= 0.f && mx < (float)p.map_w && my >= 0.f && my < (float)p.map_h)
-                x = p.maps[((size_t)m * p.n_sem + p.layer) * p.map_h * p.map_w + (size_t)my * p.map_w + (size_t)mx];
-        }
+        if (lane < 52) mdev::disk_sample(p, ri, lane, fu, fv);
+        const float x = mdev::raster_value(p, sc, xi, yi, c, s, fu, fv);      // raster_kernel's semantic plane, for this one pixel
         const unsigned long long bad = __ballot(lane <= 52 && x == 0.f);
         off = (unsigned int)((bad >> 52) & 1ull);
         dsk = (bad & ((1ull << 52) - 1ull)) ? 1u : 0u;
@@ -121,13 +90,9 @@ __global__ __launch_bounds__(kWaves * 64) void scene_metrics_step_kernel(const M
                 const float xj = p.world[(size_t)j * 3], yj = p.world[(size_t)j * 3 + 1], hj = p.world[(size_t)j * 3 + 2];
                 const float e0 = p.extent[(size_t)j * 3], e1 = p.extent[(size_t)j * 3 + 1];
                 if (!(isnan(xj) || isnan(yj))) {
-                    const float dx = xj - xi, dy = yj - yi, b0 = 0.5f * e0, b1 = 0.5f * e1;
-                    dhit = sqrtf(dx * dx + dy * dy) < ri + 0.5f * fminf(e0, e1);
-                    // separating axes: the two edge normals of each box
-                    const float cj = cosf(hj), sj = sinf(hj);
-                    const float cc = fabsf(c * cj + s * sj), cs = fabsf(c * sj - s * cj);      // |u_i . u_j| = |v_i . v_j|, |u_i . v_j| = |v_i . u_j|
-                    bhit = fabsf(dx * c + dy * s) <= a0 + b0 * cc + b1 * cs && fabsf(dy * c - dx * s) <= a1 + b0 * cs + b1 * cc &&
-                           fabsf(dx * cj + dy * sj) <= b0 + a0 * cc + a1 * cs && fabsf(dy * cj - dx * sj) <= b1 + a0 * cs + a1 * cc;
+                    float dist, rsum;
+                    mdev::pair_hits(xi, yi, c, s, a0, a1, ri, xj, yj, hj, e0, e1, dist, rsum, bhit);
+                    dhit = dist < rsum;
                 }
             }
             if (__ballot(dhit)) disk_hit = 1u;

@@ -1154,6 +1154,82 @@ class Engine:
                                                         self._stream()), "cld_scene_metrics_read")
         return per_agent, per_scene
 
+    # ------------------------------------------------------------------ guidance satisfaction metrics (guidance_metrics.py)
+    def guide_metrics_setup(self, scene_start, extent, entries, maps=None, scene_map=None, map_from_world=None, drivable_layer: int = 0,
+                            height: int = 224, width: int = 224, px_per_m: float = 2.0, ego_center=(-0.5, 0.0),
+                            no_map_fill: float = -1.0, n_sem: int = 3):
+        """The `cld_guide_metrics` struct of a scene set and an entry table (include/cld.h) -> (struct, B_all, num_scenes, num_entries,
+        num_members, the tensors it points to).  `entries`: one dict per metric object with `kind` (a name of _lib.GUIDE_METRIC_KINDS or
+        its number), `scene`, `members` (batch rows), optionally `excluded` (batch rows; sorted here) and `params` (floats, the layout of
+        include/cld.h).  The table is checked here on the host -- the library never validates the contents of device memory -- and
+        laid out as flat device arrays once; the scene set is checked as `scene_metrics_setup` checks it."""
+        base, B_all, S, keep = self.scene_metrics_setup(scene_start, extent, maps, scene_map, map_from_world, drivable_layer=drivable_layer,
+                                                        height=height, width=width, px_per_m=px_per_m, ego_center=ego_center,
+                                                        no_map_fill=no_map_fill, n_sem=n_sem)
+        entries = list(entries)
+        if not entries:
+            raise CldError("guide metrics: no entry (every scene's guidance list is empty)")
+        kinds, scenes, members, excluded, params = [], [], [], [], []
+        ms, xs, ps = [0], [0], [0]
+        for n, ent in enumerate(entries):
+            kind = ent["kind"]
+            kind = _lib.GUIDE_METRIC_KINDS.get(kind, kind) if isinstance(kind, str) else int(kind)
+            if kind not in _lib.GUIDE_METRIC_KINDS.values():
+                raise CldError(f"guide metrics: entry {n} has unknown kind {ent['kind']!r} (one of {sorted(_lib.GUIDE_METRIC_KINDS)})")
+            sc = int(ent["scene"])
+            mem = [int(r) for r in ent["members"]]
+            exc = sorted(int(r) for r in (ent.get("excluded") or ()))
+            if not 0 <= sc < S:
+                raise CldError(f"guide metrics: entry {n} scores scene {sc}, there are {S}")
+            if not mem or min(mem + exc) < 0 or max(mem + exc) >= B_all:
+                raise CldError(f"guide metrics: entry {n} needs at least one member, and rows within [0, {B_all})")
+            kinds.append(kind); scenes.append(sc)
+            members += mem; excluded += exc; params += [float(v) for v in (ent.get("params") or ())]
+            ms.append(len(members)); xs.append(len(excluded)); ps.append(len(params))
+        i32 = lambda v: torch.tensor(v, dtype=torch.int32).to(self.device)
+        t = dict(kind=i32(kinds), scene=i32(scenes), ms=i32(ms), members=i32(members), xs=i32(xs), ps=i32(ps),
+                 excluded=i32(excluded) if excluded else None,
+                 params=torch.tensor(params, dtype=torch.float64).to(self.device) if params else None)
+        dp = lambda x: None if x is None else x.data_ptr()
+        st = _lib.CldGuideMetrics(base.extent, base.scene_start, base.maps, base.scene_map, base.map_from_world, dp(t["kind"]),
+                                  dp(t["scene"]), dp(t["ms"]), dp(t["members"]), dp(t["xs"]), dp(t["excluded"]), dp(t["ps"]),
+                                  dp(t["params"]), len(kinds), len(members), len(excluded), len(params), S, B_all, base.n_sem,
+                                  base.height, base.width, base.num_maps, base.map_h, base.map_w, base.drivable_layer, base.px_per_m,
+                                  base.ego_center, base.no_map_fill)
+        return st, B_all, S, len(kinds), len(members), (keep, t)
+
+    def guide_metrics_state(self, setup):
+        """An empty state buffer for the entry table of `setup` (cld_guide_metrics_state_bytes; all-zero = empty)."""
+        return torch.zeros(int(self.lib.cld_guide_metrics_state_bytes(setup[3], setup[4])), dtype=torch.uint8, device=self.device)
+
+    def _guide_metrics_state(self, setup, state):
+        need = int(self.lib.cld_guide_metrics_state_bytes(setup[3], setup[4]))
+        if not (isinstance(state, torch.Tensor) and state.device == self.device and state.dtype == torch.uint8 and state.is_contiguous()
+                and state.numel() == need):
+            raise CldError(f"guide metrics: state must be a contiguous uint8 tensor of {need} bytes on {self.device} (guide_metrics_state)")
+        return state
+
+    def guide_metrics_step(self, setup, world, speed, acc, state, global_t: int):
+        """One environment step of the guidance metrics (cld_guide_metrics_step): world [B_all,3], speed [B_all], acc [B_all] -> `state`
+        updated in place.  One launch, no host synchronisation."""
+        st, B_all = setup[0], setup[1]
+        state = self._guide_metrics_state(setup, state)
+        world, speed, acc = self._f32(world, (B_all, 3)), self._f32(speed, (B_all,)), self._f32(acc, (B_all,))
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cld_guide_metrics_step(self._h, C.byref(st), _ptr(world), _ptr(speed), _ptr(acc), _ptr(state),
+                                                        int(global_t), self._stream()), "cld_guide_metrics_step")
+
+    def guide_metrics_read(self, setup, state):
+        """cld_guide_metrics_read -> (per_entry [num_entries], per_member [num_members]) float64; include/cld.h defines them."""
+        st, E, M = setup[0], setup[3], setup[4]
+        state = self._guide_metrics_state(setup, state)
+        per_entry = torch.empty(E, dtype=torch.float64, device=self.device)
+        per_member = torch.empty(M, dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cld_guide_metrics_read(self._h, C.byref(st), _ptr(state), _ptr(per_entry), _ptr(per_member),
+                                                        self._stream()), "cld_guide_metrics_read")
+        return per_entry, per_member
+
     # ------------------------------------------------------------------ occupancy coverage and diversity (env_metrics.py:977-1218)
     def occupancy_setup(self, scene_start, window, offset, step=(2.0, 2.0), sigma: float = 1.0, kernel_cut: float = 0.1, maps=None,
                         scene_map=None, map_from_world=None, drivable_layer: int = 0, no_map_fill: float = -1.0, n_sem: int = 3):

@@ -14,6 +14,10 @@ problem of the diversity value leaves the device (`emd_linprog`).
 `RealismDeviation` is the test stage's other number (src/trainers/guide_dm_trainer.py:204-295): the mean Wasserstein-1 distance between
 ground truth and prediction of three quantities, accumulated and evaluated on the device (`cld_realism_terms`, `cld_sort_f32`,
 `cld_wasserstein_f32`; csrc/realism_kernels.hip).
+
+`GuidanceMetrics` says whether the guidance worked: upstream's guidance satisfaction metrics (src/tbsim/utils/guidance_metrics.py), one
+to three per entry of the guidance config `set_guidance` takes, under upstream's keys `guide_<metric>_s<scene>g<config>`; one launch per
+environment step (`cld_guide_metrics_step` / `cld_guide_metrics_read`; csrc/guide_metrics_kernels.hip).
 """
 from __future__ import annotations
 
@@ -74,7 +78,9 @@ class RolloutMetrics:
 
     def add_plans(self, plans_all):
         """The `n_step_action` executed states of every agent's plan [B_all,52,6] (agent frame at planning time), taken to the world
-        as `SceneObserver.advance` takes them, each scored as one environment step; the poses move to the last of them."""
+        as `SceneObserver.advance` takes them, each scored as one environment step; the poses move to the last of them.  These are the
+        states AFTER each action; `GuidanceMetrics.add_plans` scores the states BEFORE each action, as upstream's environment feeds its
+        guidance metrics."""
         plans = torch.as_tensor(plans_all).to(self.engine.device, torch.float32).contiguous()
         if tuple(plans.shape) != (self.B_all, 52, 6):
             raise CldError(f"RolloutMetrics: plans must cover all {self.B_all} agents as [{self.B_all},52,6], got {tuple(plans.shape)}")
@@ -439,3 +445,212 @@ class RealismDeviation:
         e = self.engine
         wd = [e.wasserstein_distance(e.sort(v["gt"][n]), e.sort(v["pred"][n]), presorted=True) for n in self.NAMES]
         return {"wd_long": wd[0], "wd_lat": wd[1], "wd_jerk": wd[2], "realism_deviation": (wd[0] + wd[1] + wd[2]) / 3.0}
+
+
+# upstream's GUIDANCE_NAME_TO_METRICS (guidance_metrics.py:876-894) for the names built here, in its order; stop_sign and global_stop_sign
+# need stlcg and the gpt* names a language-model front end: neither their losses nor their metrics are built
+GUIDANCE_NAME_TO_METRICS = {
+    "target_speed": ("target_speed",),
+    "agent_collision": ("agent_collision_disk", "social_dist", "agent_collision"),
+    "map_collision": ("map_collision", "map_collision_disk"),
+    "target_pos_at_time": ("target_pos_at_time",),
+    "target_pos": ("target_pos",),
+    "global_target_pos_at_time": ("global_target_pos_at_time",),
+    "global_target_pos": ("global_target_pos",),
+    "social_group": ("social_group",),
+    "speed_limit": ("speed_limit",),
+    "acc_limit": ("acc_limit",),
+}
+
+
+def guidance_metric_names(guidance_config_list, constraint_config=None):
+    """The keys `guidance_metrics_from_config(guidance_config_list)` registers, in its order, then those of
+    `constraint_metrics_from_config(constraint_config)` (guidance_metrics.py:896-929).  Host only.  A name outside
+    GUIDANCE_NAME_TO_METRICS raises ValueError("Unknown guidance metric: ..."), as upstream does."""
+    keys = []
+    for si, cfgs in enumerate(guidance_config_list):
+        for ci, cfg in enumerate(cfgs):
+            if cfg["name"] not in GUIDANCE_NAME_TO_METRICS:
+                raise ValueError("Unknown guidance metric: {}".format(cfg["name"]))
+            keys += ["guide_%s_s%dg%d" % (met, si, ci) for met in GUIDANCE_NAME_TO_METRICS[cfg["name"]]]
+    for si, cfg in enumerate(constraint_config or ()):
+        if cfg:
+            keys.append("guide_constraint_s%d" % si)
+    return keys
+
+
+def guidance_metric_table(guidance_config_list, scene_start, constraint_config=None):
+    """The entry table of `cld_guide_metrics` (include/cld.h) on the host: one dict per key of `guidance_metric_names`, in its order:
+    `key`, `kind` (upstream's metric name), `scene`, `config` (index in the scene's list, None for a constraint), `members` (batch rows:
+    the config's scene-local `agents` shifted by the scene's first row, or the whole scene), `excluded` (the batch rows of
+    params['excluded_agents'] that lie in this scene, sorted), `excluded_local` (the same as scene-local indices, what upstream's metric
+    classes take) and `params` (the flat float64 list of include/cld.h; a target_speed [B_all, L] indexed by batch row is sliced to the
+    members' rows here, which is what upstream's TargetSpeedGuidance needs to be handed)."""
+    import numpy as np
+    ss = [int(v) for v in np.asarray(torch.as_tensor(scene_start).cpu()).reshape(-1)]
+    S = len(ss) - 1
+    if len(guidance_config_list) != S:
+        raise ValueError(f"guidance config list must hold one entry per scene ({S}), got {len(guidance_config_list)}")
+    if constraint_config is not None and len(constraint_config) != S:
+        raise ValueError(f"constraint config must hold one entry per scene ({S}), got {len(constraint_config)}")
+    guidance_metric_names(guidance_config_list, constraint_config)          # (unknown names raise before anything is built)
+
+    def rows(si, agents):
+        n = ss[si + 1] - ss[si]
+        local = list(range(n)) if agents is None else [int(a) for a in agents]
+        if not local or min(local) < 0 or max(local) >= n:
+            raise ValueError(f"scene {si}: `agents` {agents} must name at least one of its {n} agents")
+        return [ss[si] + a for a in local]
+
+    def waypoints(si, name, pos, times, n):
+        pos = np.asarray(pos, np.float64).reshape(-1, 2)
+        if pos.shape[0] != n:
+            raise ValueError(f"scene {si}: {name} needs one position per agent of the config ({n}), got {pos.shape[0]}")
+        out = [float(v) for v in pos.reshape(-1)]
+        if times is not None:
+            t = np.asarray(times, np.float64).reshape(-1)
+            if t.size not in (1, n):
+                raise ValueError(f"scene {si}: {name} needs one time per agent of the config ({n}), got {t.size}")
+            out += [float(v) for v in np.broadcast_to(t, (n,))]
+        return out
+
+    table = []
+    for si, cfgs in enumerate(guidance_config_list):
+        for ci, cfg in enumerate(cfgs):
+            name, prm = cfg["name"], cfg.get("params") or {}
+            members = rows(si, cfg.get("agents"))
+            n = len(members)
+            excl = sorted({int(b) for b in (prm.get("excluded_agents") or ()) if ss[si] <= int(b) < ss[si + 1]})
+            for met in GUIDANCE_NAME_TO_METRICS[name]:
+                params = []
+                if met == "target_speed":
+                    ts = np.asarray(torch.as_tensor(prm["target_speed"]).cpu(), np.float64)
+                    if ts.ndim != 2 or ts.shape[0] < ss[-1]:
+                        raise ValueError(f"scene {si}: target_speed must be [B_all = {ss[-1]}, L] (indexed by batch row), got {ts.shape}")
+                    params = [float(ts.shape[1])] + [float(v) for v in ts[members].reshape(-1)]
+                elif met in ("speed_limit", "acc_limit"):
+                    params = [float(prm[met])]
+                elif met == "social_dist":
+                    params = [float(prm.get("buffer_dist", 0.2))]               # the default of guidance_from_config
+                elif met == "social_group":
+                    params = [float(prm["social_dist"])]
+                elif met in ("target_pos", "global_target_pos"):
+                    params = waypoints(si, met, prm["target_pos"], None, n)
+                elif met in ("target_pos_at_time", "global_target_pos_at_time"):
+                    params = waypoints(si, met, prm["target_pos"], prm["target_time"], n)
+                uses_excl = met in ("agent_collision", "agent_collision_disk", "social_dist")
+                table.append(dict(key="guide_%s_s%dg%d" % (met, si, ci), kind=met, scene=si, config=ci, members=members,
+                                  excluded=excl if uses_excl else [], excluded_local=[b - ss[si] for b in excl] if uses_excl else [],
+                                  params=params))
+    for si, cfg in enumerate(constraint_config or ()):
+        if not cfg:
+            continue
+        members = rows(si, cfg.get("agents"))
+        table.append(dict(key="guide_constraint_s%d" % si, kind="target_pos_at_time", scene=si, config=None, members=members, excluded=[],
+                          excluded_local=[], params=waypoints(si, "constraint", cfg["locs"], cfg["times"], len(members))))
+    return table
+
+
+class GuidanceMetrics:
+    """Upstream's guidance satisfaction metrics on the device (src/tbsim/utils/guidance_metrics.py; include/cld.h
+    `cld_guide_metrics_step` defines every quantity and the deliberate differences).
+
+    `guidance_config_list` is exactly what `set_guidance` / `guidance_from_config` take: one list per scene (the scenes of other ranks
+    included; a scene with an empty list has no entry) of {'name', 'weight', 'params', 'agents'}; `agents` are scene-local indices,
+    params['excluded_agents'] are BATCH rows and params['target_speed'] is [B_all, L] indexed by batch row.  Upstream's metric classes
+    index the last two by scene-local agent instead; the conversion happens here on the host, once (`guidance_metric_table`).
+    `constraint_config`: per scene None or {'locs', 'times', 'agents'} (constraint_metrics_from_config).  scene_start, extent, maps /
+    scene_map / map_from_world and `raster_cfg` as `RolloutMetrics` takes them; world0 [B_all,3], curr_speed0 / acc0 [B_all] (default
+    zeros) are the state the first plans start from.
+
+    Feed it with `add_step(world, speed, acc)` per environment step or `add_plans(plans_all)` per plan, or pass it in `metrics=` of
+    `closed_loop_rollout` (e.g. `metrics=(rm, occ, gm)`).  Nothing synchronises before a value is read."""
+
+    def __init__(self, engine, guidance_config_list, scene_start, extent, world0, curr_speed0=None, acc0=None, maps=None, scene_map=None,
+                 map_from_world=None, constraint_config=None, n_step_action: int = 5, drivable_layer: int = 0, **raster_cfg):
+        unknown = sorted(set(raster_cfg) - set(_RASTER_KEYS))
+        if unknown:
+            raise TypeError(f"GuidanceMetrics: unknown raster settings {unknown} (one of {sorted(_RASTER_KEYS)})")
+        self.engine = engine
+        self.cfg = {k: raster_cfg.get(k, RASTER_DEFAULTS[k]) for k in _RASTER_KEYS}
+        self.n_step_action = int(n_step_action)
+        if not 1 <= self.n_step_action <= 52:
+            raise CldError(f"GuidanceMetrics: n_step_action = {n_step_action} (1 .. 52)")
+        self.table = guidance_metric_table(guidance_config_list, scene_start, constraint_config)
+        self.keys = [t["key"] for t in self.table]
+        self._setup = engine.guide_metrics_setup(scene_start, extent, self.table, maps, scene_map, map_from_world,
+                                                 drivable_layer=drivable_layer, **self.cfg)
+        self.B_all, self.num_scenes = self._setup[1], self._setup[2]
+        self._index = {k: n for n, k in enumerate(self.keys)}
+        starts = [0]
+        for t in self.table:
+            starts.append(starts[-1] + len(t["members"]))
+        self._member_start = starts
+        self._entry_scene = torch.tensor([t["scene"] for t in self.table], dtype=torch.int64, device=engine.device)
+        self.state = engine.guide_metrics_state(self._setup)
+        self.steps = 0
+        self.poses = self.speed = self.acc = None
+        self._carry(world0, curr_speed0, acc0)
+
+    def _carry(self, world, speed, acc):
+        dev, B = self.engine.device, self.B_all
+        if world is not None:
+            w = torch.as_tensor(world).to(dev, torch.float32).contiguous().clone()
+            if tuple(w.shape) != (B, 3):
+                raise CldError(f"GuidanceMetrics: world0 must be [{B},3], got {tuple(w.shape)}")
+            self.poses = w
+        for name, v in (("speed", speed), ("acc", acc)):
+            if v is None:
+                if getattr(self, name) is None:
+                    setattr(self, name, torch.zeros(B, dtype=torch.float32, device=dev))
+                continue
+            v = torch.as_tensor(v).to(dev, torch.float32).contiguous().clone()
+            if tuple(v.shape) != (B,):
+                raise CldError(f"GuidanceMetrics: curr_speed0 / acc0 must be [{B}], got {tuple(v.shape)}")
+            setattr(self, name, v)
+
+    def reset(self, world0=None, curr_speed0=None, acc0=None):
+        """Empty the state (and optionally set the state the next plans start from)."""
+        self.state.zero_()
+        self.steps = 0
+        self._carry(world0, curr_speed0, acc0)
+
+    def add_step(self, world, speed, acc):
+        """One environment step: world [B_all,3] (x, y, h; NaN x or y = the agent is absent), speed [B_all], acc [B_all].  One launch,
+        global_t = the steps fed so far, no host synchronisation."""
+        self.engine.guide_metrics_step(self._setup, world, speed, acc, self.state, self.steps)
+        self.steps += 1
+
+    def add_plans(self, plans_all):
+        """One plan [B_all,52,6] in upstream's order: the environment scores the state BEFORE each of its `n_step_action` actions
+        (env_trajdata._step:411-424), so this scores the current pose with its carried speed and acceleration, then the executed states
+        0 .. n_step_action - 2 (speed = plans[:, k, 2], acc = plans[:, k, 4]), and carries state n_step_action - 1 into the next call.
+        The first scored state of an episode is therefore the initial pose, which ConstraintGuidance's `times + 1` and
+        TargetSpeedGuidance's global_t assume.  `RolloutMetrics.add_plans` scores the states AFTER each action instead."""
+        plans = torch.as_tensor(plans_all).to(self.engine.device, torch.float32).contiguous()
+        if tuple(plans.shape) != (self.B_all, 52, 6):
+            raise CldError(f"GuidanceMetrics: plans must cover all {self.B_all} agents as [{self.B_all},52,6], got {tuple(plans.shape)}")
+        centroid, yaw = self.poses[:, :2].contiguous(), self.poses[:, 2].contiguous()
+        self.add_step(self.poses, self.speed, self.acc)
+        n = self.n_step_action
+        for k in range(n):
+            world = self.engine.world_step(plans, centroid, yaw, k)[0]
+            speed, acc = plans[:, k, 2].contiguous(), plans[:, k, 4].contiguous()
+            if k < n - 1:
+                self.add_step(world, speed, acc)
+        self.poses, self.speed, self.acc = world, speed, acc
+
+    def get_episode_metrics(self):
+        """-> {key: [num_scenes] float64 device tensor, NaN except at the entry's scene}, upstream's keys in upstream's order."""
+        per_entry = self.engine.guide_metrics_read(self._setup, self.state)[0]
+        out = torch.full((len(self.keys), self.num_scenes), float("nan"), dtype=torch.float64, device=self.engine.device)
+        out[torch.arange(len(self.keys), device=self.engine.device), self._entry_scene] = per_entry
+        return {k: out[n] for n, k in enumerate(self.keys)}
+
+    def per_member(self, key: str):
+        """-> [members of the entry] float64 device tensor: the member's episode value (include/cld.h `cld_guide_metrics_read`), in the
+        order of the config's `agents`."""
+        if key not in self._index:
+            raise KeyError(f"GuidanceMetrics.per_member: no metric {key!r} (one of {self.keys})")
+        e = self._index[key]
+        return self.engine.guide_metrics_read(self._setup, self.state)[1][self._member_start[e]:self._member_start[e + 1]]

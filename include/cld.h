@@ -581,6 +581,106 @@ int cld_scene_metrics_read(cld_handle h, const cld_scene_metrics* m, const void*
                            float* per_agent /*[B_all, CLD_METRICS_AGENT_COLS] or NULL*/,
                            float* per_scene /*[num_scenes, CLD_METRICS_SCENE_COLS] or NULL*/, void* stream);
 
+/* The guidance satisfaction metrics of a closed-loop rollout, kept on the device: what upstream's guidance_metrics_from_config /
+ * constraint_metrics_from_config register, one to three GuidanceMetric objects per entry of the guidance config
+ * (src/tbsim/utils/guidance_metrics.py), fed once per 0.1 s environment step.  Needs no weights; one launch per step, no atomics (two runs
+ * give the same bytes), no synchronisation.  All pointers are DEVICE.
+ *
+ * The entry table (built once by the caller; E = num_entries, one ENTRY per registered metric object):
+ *   entry_kind [E]      CLD_GM_* below;  entry_scene [E] the scene the entry scores;
+ *   member_start [E+1]  into members [num_members]: the batch rows the entry scores (the config's `agents`, or the whole scene), in the
+ *                       config's order; a MEMBER is one (entry, row) slot, k = its index within the entry, n = the entry's member count;
+ *   excl_start [E+1]    into excluded [num_excluded]: the entry's excluded batch rows, SORTED ASCENDING within the entry (binary search);
+ *                       excluded may be NULL when num_excluded = 0;
+ *   param_start [E+1]   into params [num_params] (double); per kind:
+ *                         TARGET_SPEED  L, then ts[n, L] member-major (L = the row length);   SPEED_LIMIT, ACC_LIMIT  the limit;
+ *                         SOCIAL_DIST  buffer_dist;   SOCIAL_GROUP  social_dist;   the two TARGET_POS kinds  pos[n, 2];
+ *                         the two AT_TIME kinds  pos[n, 2], then target_time[n];   the other kinds none.
+ *                       A parameter read past its entry's range is NaN; params may be NULL when num_params = 0.
+ * Table CONTENTS are never validated (device memory): every index read from it is clamped into its array, so a malformed table cannot
+ * make the kernels read or write out of bounds, but its metrics are then meaningless.
+ *
+ * cld_guide_metrics_step is one environment step: world [B_all,3] (x, y, h), speed [B_all], acc [B_all] (the executed state's speed and
+ * acceleration columns), global_t = the index of this step in the episode.  `state` is cld_guide_metrics_state_bytes(E, num_members)
+ * bytes, 16-byte aligned, all-zero = empty, updated in place, opaque.  Member row i is ABSENT at a step when its x or y is NaN.
+ * Flags are decided in fp32 with the arithmetic of cld_scene_metrics_step (disk test, separating-axis test, partner rule, map pixel
+ * lookup, the 52 disk samples): without exclusions and with whole-scene members, the disk and box flags equal coll_disk / coll_any /
+ * off_road_disk of cld_scene_metrics_step bit for bit.  Distances, differences and sums are fp64 from the fp32 inputs, every operation
+ * rounded on its own (no fused multiply-add); reductions run in a fixed order.  Per step and member:
+ *   TARGET_SPEED (TargetSpeedGuidance)  |speed - ts[k, global_t]|, 0 once global_t >= L; the step value is the nanmean over members;
+ *   SPEED_LIMIT, ACC_LIMIT (SpeedLimitGuidance, AccLimitGuidance)  max(speed - limit, 0), max(|acc| - limit, 0), a NaN kept (np.clip);
+ *                 the step value is the mean over members (NaN if any is).  Episode value of the three: the mean of the step values.
+ *   AGENT_COLLISION (AgentCollisionGuidance)  1 when the member's box overlaps a valid j != i of the scene, UNLESS the member and the
+ *                 lowest-index such j are both excluded.  Absent: 0.  Episode: mean over members of the max over steps.
+ *   AGENT_COLLISION_DISK, SOCIAL_DIST (AgentCollisionGuidanceDisk, SocialDistanceGuidance)  1 when some valid, not excluded j != i of
+ *                 the scene has |p_i - p_j| < r_i + r_j (SOCIAL_DIST: (r_i + r_j) + buffer_dist, the buffer rounded to fp32);
+ *                 an excluded or absent member records 0.  Episode: the same.
+ *   MAP_COLLISION (MapCollisionGuidance -> Metrics.batch_detect_off_road_boxes)  the four corners (ox -+ ppm e0 / 2, oy -+ ppm e1 / 2) in
+ *                 get_box_world_coords' order (-,-) (-,+) (+,+) (+,-) on the raster of an agent standing at this step's pose (yaw 0 in its
+ *                 own raster), each clamped to the raster, rounded half to even, clamped again; 1 if drv(i; u, v) = 0 at any of them.
+ *   MAP_COLLISION_DISK (MapCollisionGuidanceDisk)  off_road_disk of cld_scene_metrics_step.
+ *                 Episode value of the two: mean over members of (flags summed over steps / steps).  An absent member records 0 and
+ *                 stays in the denominator: PARITY UNPINNED, upstream casts a NaN pixel index there.
+ *   GLOBAL_TARGET_POS (GlobalTargetPosGuidance)  d = |p - pos[k]|; the member keeps min d under a strict <, so a NaN never wins.
+ *   TARGET_POS (TargetPosGuidance)  the same on p taken through agent_from_world of the member's pose at the state's FIRST step:
+ *                 with c = cos h0, s = sin h0 in double, rows (c, s, -(c x0) - (s y0)) and (-s, c, (s x0) - (c y0)), applied as
+ *                 (x m0 + y m1) + m2.  Episode value of the two: mean over members of the minimum (inf while none was taken).
+ *   GLOBAL_TARGET_POS_AT_TIME, TARGET_POS_AT_TIME (GlobalConstraintGuidance, ConstraintGuidance; also the `constraint` entries)
+ *                 at the step with global_t = target_time[k] + 1 (the first scored step is the initial state) the distance to pos[k]
+ *                 (world / first-step frame) is captured.  Episode: mean over members; NaN when a member's step never came or it was
+ *                 absent then (upstream raises an IndexError for a time beyond the episode).
+ *   SOCIAL_GROUP (SocialGroupGuidance)  |min over the entry's other members of |p_i - p_j| - social_dist|; a NaN distance makes the minimum
+ *                 NaN, an entry of one member gives inf.  Episode: mean over members of the mean over steps.
+ * cld_guide_metrics_read finalises (either output may be NULL): per_member [num_members] the member's episode value (for the per-step-mean
+ * kinds the mean of its own terms), per_entry [E] the episode value.  The mean over members is taken in numpy's add.reduce order (its
+ * pairwise sum: halves down to blocks of at most 128, eight accumulators per block), so a mean of step fractions is np.mean's bits.  An empty state reads NaN (inf for the
+ * two TARGET_POS kinds), an unknown kind NaN.
+ * DIFFERENCES from upstream, deliberate: (1) AgentCollisionGuidance compares coll[1], an index into the OTHER-agents array, with
+ * excluded_agents: off by one for partners above the agent; here the partner is its row.  (2) The map kinds read the raster of the agent
+ * at the step's pose, as cld_scene_metrics does; upstream reads the observation raster, which may be stale.  (3) Box overlap is this
+ * library's separating-axis test; upstream decides with shapely: PARITY UNPINNED as for cld_scene_metrics.  (4) ACC_LIMIT reads the executed
+ * state's acceleration; upstream reads trajdata's agent_hist[..., 4] / agent_hist[..., 7].
+ * CLD_ERR_ARG: NULL m / world / speed / acc / state / extent / scene_start / entry arrays, num_entries or num_members < 1, num_members or
+ * B_all beyond CLD_RASTER_MAX_AGENTS, num_excluded or num_params < 0 or > 0 without their array, the raster and map checks of
+ * cld_scene_metrics_step, global_t < 0, read without an output. */
+#define CLD_GM_TARGET_SPEED 0
+#define CLD_GM_SPEED_LIMIT 1
+#define CLD_GM_ACC_LIMIT 2
+#define CLD_GM_AGENT_COLLISION 3
+#define CLD_GM_AGENT_COLLISION_DISK 4
+#define CLD_GM_SOCIAL_DIST 5
+#define CLD_GM_MAP_COLLISION 6
+#define CLD_GM_MAP_COLLISION_DISK 7
+#define CLD_GM_TARGET_POS 8
+#define CLD_GM_GLOBAL_TARGET_POS 9
+#define CLD_GM_TARGET_POS_AT_TIME 10
+#define CLD_GM_GLOBAL_TARGET_POS_AT_TIME 11
+#define CLD_GM_SOCIAL_GROUP 12
+typedef struct cld_guide_metrics {
+    const float*   extent;          /* DEVICE [B_all, 3] */
+    const int32_t* scene_start;     /* DEVICE [num_scenes + 1] */
+    const float*   maps;            /* DEVICE [num_maps, n_sem, map_h, map_w] or NULL */
+    const int32_t* scene_map;       /* DEVICE [num_scenes], < 0: no map */
+    const float*   map_from_world;  /* DEVICE [num_maps, 3, 3] */
+    const int32_t* entry_kind;      /* DEVICE [num_entries] */
+    const int32_t* entry_scene;     /* DEVICE [num_entries] */
+    const int32_t* member_start;    /* DEVICE [num_entries + 1] */
+    const int32_t* members;         /* DEVICE [num_members] */
+    const int32_t* excl_start;      /* DEVICE [num_entries + 1] */
+    const int32_t* excluded;        /* DEVICE [num_excluded] or NULL */
+    const int32_t* param_start;     /* DEVICE [num_entries + 1] */
+    const double*  params;          /* DEVICE [num_params] or NULL */
+    int32_t num_entries, num_members, num_excluded, num_params;
+    int32_t num_scenes, B_all, n_sem, height, width, num_maps, map_h, map_w, drivable_layer;
+    float   px_per_m, ego_center[2], no_map_fill;
+} cld_guide_metrics;
+
+size_t cld_guide_metrics_state_bytes(int32_t num_entries, int32_t num_members);
+int cld_guide_metrics_step(cld_handle h, const cld_guide_metrics* m, const float* world /*[B_all,3]*/, const float* speed /*[B_all]*/,
+                           const float* acc /*[B_all]*/, void* state, int32_t global_t, void* stream);
+int cld_guide_metrics_read(cld_handle h, const cld_guide_metrics* m, const void* state, double* per_entry /*[num_entries] or NULL*/,
+                           double* per_member /*[num_members] or NULL*/, void* stream);
+
 /* The occupancy metrics of a closed-loop evaluation, kept on the device: what upstream registers as all_coverage = OccupancyCoverage (grid
  * step 2 m) and all_diversity = OccupancyDiversity (grid step 4 m) (src/tbsim/evaluation/env_builders.py:35-52; the classes and their
  * OccupancyGrid: src/tbsim/envs/env_metrics.py:977-1218).  Needs no weights; plain fp64 / integers in both library precisions; none of the
