@@ -101,6 +101,17 @@ class CldGoal(C.Structure):
                 ("num_samp", C.c_int32), ("global_t", C.c_int32), ("dt", C.c_float), ("min_progress_dist", C.c_float)]
 
 
+class CldSocialGroup(C.Structure):
+    """include/cld.h `cld_social_group` (upstream's SocialGroupLoss over all groups of a batch, device pointers)."""
+    _fields_ = [("group_start", C.c_void_p), ("member", C.c_void_p), ("leader", C.c_void_p), ("social_dist", C.c_void_p),
+                ("cohesion", C.c_void_p), ("scale", C.c_void_p), ("world_from_agent", C.c_void_p), ("draw_r", C.c_void_p),
+                ("draw_u", C.c_void_p), ("seed", C.c_uint64), ("num_groups", C.c_int32), ("num_samp", C.c_int32),
+                ("max_members", C.c_int32), ("iter_base", C.c_int32), ("n_iter", C.c_int32), ("n_opt", C.c_int32)]
+
+
+SOCIAL_MAX_MEMBERS = 128               # include/cld.h: the bound on cld_social_group.max_members
+
+
 class CldRaster(C.Structure):
     """include/cld.h `cld_raster` (the scene an observation raster is built from, device pointers)."""
     _fields_ = [("hist_world", C.c_void_p), ("hist_avail", C.c_void_p), ("scene_start", C.c_void_p), ("maps", C.c_void_p),
@@ -194,6 +205,8 @@ SIGNATURES = {
     "cld_map_collision_loss": (C.c_int, [_P, _P, C.POINTER(CldMapCollision), _P, _P, _P, C.c_int32, _P]),
     "cld_goal_loss": (C.c_int, [_P, _P, C.POINTER(CldGoal), _P, _P, _P, C.c_int32, _P]),
     "cld_set_goal_term": (C.c_int, [_P, C.POINTER(CldGoal)]),
+    "cld_social_group_loss": (C.c_int, [_P, _P, C.POINTER(CldSocialGroup), _P, _P, _P, C.c_int32, _P]),
+    "cld_set_social_term": (C.c_int, [_P, C.POINTER(CldSocialGroup)]),
     "cld_set_map_source": (C.c_int, [_P, C.POINTER(CldMapSource)]),
     "cld_world_step": (C.c_int, [_P, _P, _P, _P, C.c_int32, _P, _P, C.c_int32, _P]),
     "cld_rasterize": (C.c_int, [_P, C.POINTER(CldRaster), C.c_int32, C.c_int32, _P, _P, _P, _P]),

@@ -54,6 +54,8 @@ struct cld_handle_s {
     bool finalized = false, has_decoder = false, has_unet = false;
     cld_goal goal{};                                 // cld_set_goal_term: the goal term every guided call adds while has_goal
     bool has_goal = false;
+    cld_social_group social{};                       // cld_set_social_term: the social-group term every guided call adds while has_social
+    bool has_social = false;
     cld_map_source map_source{};                     // cld_set_map_source: what a cld_map_collision without a drivable_map reads while has_map_source
     bool has_map_source = false;
     std::vector<void*> dev_allocs;
@@ -1508,9 +1510,39 @@ static GoalArgs goal_args(const cld_goal* g, const float* traj, const float* gra
     return a;
 }
 
-static int check_guidance(cld_handle h, const char* fn, const cld_guidance* gd, int B) {
+// `iters` / `opt_steps`: the evaluations (loop iterations x optimiser steps) caller draws have to cover; 0 = the stand-alone loss (slab [0, 0])
+static int check_social(cld_handle h, const char* fn, const cld_social_group* t, int B, int iters, int opt_steps) {
+    if (!t->group_start || !t->member || !t->leader || !t->social_dist || !t->cohesion || !t->scale || !t->world_from_agent)
+        return fail(h, CLD_ERR_ARG, std::string(fn) + ": social-group term: null pointer");
+    if (t->num_groups < 1 || t->num_samp < 1 || B % t->num_samp || (int64_t)t->num_groups * t->num_samp > INT32_MAX)
+        return fail(h, CLD_ERR_ARG, std::string(fn) + ": social-group term: B must be agents x num_samp, num_groups >= 1");
+    if (t->max_members < 2 || t->max_members > kSocialMaxMembers)
+        return fail(h, CLD_ERR_ARG, std::string(fn) + ": social-group term: groups of 2.." + std::to_string(kSocialMaxMembers) + " members");
+    if ((t->draw_r == nullptr) != (t->draw_u == nullptr))
+        return fail(h, CLD_ERR_ARG, std::string(fn) + ": social-group term: draw_r and draw_u go together (both or neither)");
+    if (t->draw_r && (t->n_iter < std::max(iters, 1) || t->n_opt < std::max(opt_steps, 1)))
+        return fail(h, CLD_ERR_ARG, std::string(fn) + ": social-group term: caller draws [" + std::to_string(t->n_iter) + ", " + std::to_string(t->n_opt) +
+                                        ", B, 52] do not cover the call's " + std::to_string(std::max(iters, 1)) + " iterations x " +
+                                        std::to_string(std::max(opt_steps, 1)) + " optimiser steps");
+    return CLD_OK;
+}
+// evaluation (it, k): loop iteration `it` of the call, optimiser step k (from 0)
+static SocialArgs social_args(const cld_social_group* t, const float* traj, float* loss, float* grad, int B, int it, int k) {
+    SocialArgs a{};
+    a.traj = traj; a.world_from_agent = t->world_from_agent; a.group_start = t->group_start; a.member = t->member; a.leader = t->leader;
+    a.social_dist = t->social_dist; a.cohesion = t->cohesion; a.scale = t->scale;
+    if (t->draw_r) {
+        const size_t off = ((size_t)it * t->n_opt + k) * B * 52;
+        a.draw_r = t->draw_r + off; a.draw_u = t->draw_u + off;
+    }
+    a.loss = loss; a.grad = grad; a.rows = B; a.num_groups = t->num_groups; a.num_samp = t->num_samp; a.max_members = t->max_members;
+    a.seed = t->seed; a.eval = ((unsigned long long)(uint32_t)(t->iter_base + it) << 16) | (unsigned long long)k;
+    return a;
+}
+
+static int check_guidance(cld_handle h, const char* fn, const cld_guidance* gd, int B, int iters = 1) {
     if (!h->has_decoder) return fail(h, CLD_ERR_STATE, std::string(fn) + ": guidance needs the decoder weights");
-    if (!gd->curr_states || (!gd->target_speed && !gd->speed_limit_scale && !gd->acc_limit_scale && !gd->target_pos_scale && !gd->ext_grad && !gd->collision && !gd->map_collision && !h->has_goal))
+    if (!gd->curr_states || (!gd->target_speed && !gd->speed_limit_scale && !gd->acc_limit_scale && !gd->target_pos_scale && !gd->ext_grad && !gd->collision && !gd->map_collision && !h->has_goal && !h->has_social))
         return fail(h, CLD_ERR_ARG, std::string(fn) + ": guidance needs curr_states and at least one loss term");
     if (gd->collision) {
         const int rcc = check_collision(h, fn, gd->collision, B);
@@ -1526,6 +1558,10 @@ static int check_guidance(cld_handle h, const char* fn, const cld_guidance* gd, 
     }
     if (gd->grad_steps < 0 || gd->final_grad_steps < 0 || gd->grad_steps > 64 || gd->final_grad_steps > 64)
         return fail(h, CLD_ERR_ARG, std::string(fn) + ": grad_steps out of range (0..64)");
+    if (h->has_social) {
+        const int rcc = check_social(h, fn, &h->social, B, iters, std::max(gd->grad_steps, gd->final_grad_steps));
+        if (rcc) return rcc;
+    }
     if (gd->optimizer != CLD_GUIDE_ADAM && gd->optimizer != CLD_GUIDE_SGD) return fail(h, CLD_ERR_ARG, std::string(fn) + ": unknown optimizer");
     if (gd->apply_output && gd->final_optimizer != CLD_GUIDE_ADAM && gd->final_optimizer != CLD_GUIDE_SGD)
         return fail(h, CLD_ERR_ARG, std::string(fn) + ": unknown optimizer for the output step");
@@ -1558,7 +1594,7 @@ static int run_guidance(cld_handle h, const Ws& w, const cld_guidance* gd, int B
         const bool last = k == steps;
         g.opt_step = k;
         g.mean = k == 1 ? mean0 : w.gcur;
-        if (gd->collision || gd->map_collision || h->has_goal) {    // the scene / map / goal terms are functions of the decoded plans of the current iterate
+        if (gd->collision || gd->map_collision || h->has_goal || h->has_social) {    // the scene / map / goal / social terms are functions of the decoded plans of the current iterate
             if (B >= 256 && guide_forward_available(B, h->force_kernel[CLD_KERNEL_GUIDE]) && h->force_kernel[CLD_KERNEL_DECODE] == FORM_AUTO) {
                 // (from the batch size at which cld_decode itself would take its 16-agent MFMA form, ~0.3 ms; below that the
                 //  one-agent-per-workgroup decoder is the shorter chain: 64 agents 579 vs 616 us per collision-guided step)
@@ -1591,6 +1627,11 @@ static int run_guidance(cld_handle h, const Ws& w, const cld_guidance* gd, int B
         }
         if (h->has_goal) {                           // likewise: on top of the caller's ext_grad and the collision gradients
             HIPCK(h, launch_goal(goal_args(&h->goal, w.col_traj, (gd->collision || gd->map_collision) ? w.col_grad : gd->ext_grad, nullptr, w.col_grad, B), s));
+            g.ext_grad = w.col_grad;
+        }
+        if (h->has_social) {                         // after the goal term's: evaluation (loop iteration, optimiser step) picks the draws
+            const float* gin = (gd->collision || gd->map_collision || h->has_goal) ? w.col_grad : gd->ext_grad;
+            HIPCK(h, launch_social_group(social_args(&h->social, w.col_traj, nullptr, w.col_grad, B, (int)salt, k - 1), gin, s));
             g.ext_grad = w.col_grad;
         }
         g.z = last ? z : nullptr;
@@ -1665,7 +1706,7 @@ static int sample_impl(cld_handle h, const char* fn, const float* x_T, const flo
     if (!x_T || !cond) return fail(h, CLD_ERR_ARG, std::string(fn) + ": null pointer");
     if (steps != loop_steps(h))
         return fail(h, CLD_ERR_ARG, std::string(fn) + ": steps must equal len(range(0, n_timesteps, stride)) = " + std::to_string(loop_steps(h)));
-    if (gd && (rc = check_guidance(h, fn, gd, B)) != CLD_OK) return rc;
+    if (gd && (rc = check_guidance(h, fn, gd, B, steps)) != CLD_OK) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     // CFG: one 2B-agent batch per step: rows [0, bp) carry cond_feat, rows [bp, 2bp) the unconditional features,
     // both halves the same latent; the head combines the two noise predictions and rewrites both halves.
@@ -2024,6 +2065,23 @@ int cld_goal_loss(cld_handle h, const float* traj, const cld_goal* g, const floa
     int rc = check_goal(h, "cld_goal_loss", g, B);
     if (rc) return rc;
     HIPCK(h, launch_goal(goal_args(g, traj, grad_in, loss, grad, B), static_cast<hipStream_t>(stream)));
+    return CLD_OK;
+}
+
+int cld_social_group_loss(cld_handle h, const float* traj, const cld_social_group* term, const float* grad_in, float* loss, float* grad,
+                          int32_t B, void* stream) {
+    if (!h) return CLD_ERR_ARG;
+    if (!traj || !term || B < 1 || (!loss && !grad)) return fail(h, CLD_ERR_ARG, "cld_social_group_loss: bad argument");
+    int rc = check_social(h, "cld_social_group_loss", term, B, 0, 0);
+    if (rc) return rc;
+    HIPCK(h, launch_social_group(social_args(term, traj, loss, grad, B, 0, 0), grad_in, static_cast<hipStream_t>(stream)));
+    return CLD_OK;
+}
+
+int cld_set_social_term(cld_handle h, const cld_social_group* term) {
+    if (!h) return CLD_ERR_ARG;
+    h->has_social = term != nullptr;
+    h->social = term ? *term : cld_social_group{};
     return CLD_OK;
 }
 

@@ -560,6 +560,28 @@ struct GoalArgs {
 };
 hipError_t launch_goal(const GoalArgs& a, hipStream_t s);
 
+// upstream's SocialGroupLoss + its gradient w.r.t. the decoded plans (social_kernels.hip; guidance_loss.py:1137-1207)
+constexpr int kSocialMaxMembers = 128;   // the value role keeps 52 steps x 8 B per member in LDS: 54 KiB at 128 members
+struct SocialArgs {
+    const float* traj;               // [rows = A * num_samp, 52, 6] descaled plans, sample-minor
+    const float* world_from_agent;   // [A, 3, 3]
+    const int* group_start;          // [num_groups + 1] offsets into member
+    const int* member;               // [group_start[num_groups]] agent indices, ascending within a group
+    const int* leader;               // [num_groups] agent index of the detached member, or -1
+    const float* social_dist;        // [num_groups]
+    const float* cohesion;           // [num_groups]
+    const float* scale;              // [num_groups] d total / d value of a member row
+    const int* draw_r;               // [rows, 52] this evaluation's caller draws, or null (both): the on-device generator
+    const float* draw_u;             // [rows, 52]
+    float* loss;                     // [rows] or null
+    float* grad;                     // [rows, 52, 6] or null; the kernel ADDS to it (launch_social_group puts grad_in there first)
+    int rows, num_groups, num_samp;
+    int max_members;                 // what the launch sizes its LDS for: a group with more members gets NaN values and no gradient
+    unsigned long long seed, eval;   // generator key: the term's seed and the evaluation index (loop iteration << 16 | optimiser step)
+};
+// grad = grad_in (or 0) + the term's gradient; grad_in may be grad itself
+hipError_t launch_social_group(const SocialArgs& a, const float* grad_in, hipStream_t s);
+
 // PPO reward (models/rl/criticmodel.py:7-64)
 struct RewardArgs {
     const float* traj;                // [B,52,6] descaled (x, y, v, yaw, acc, yaw-rate), agent frame

@@ -331,7 +331,8 @@ class Engine:
         """dict(curr_states [B,4], target_speed [B,52] | None, loss_scale [B] | None, speed_limit (limit, scale) | None,
         acc_limit (limit, scale) | None, target_pos (pos [B,2], time index [B], scale) | None, lr | None, perturb_th | None | "sigma", optimizer "adam" | "sgd",
         grad_steps = 1, guide_clean = False, agent_collision: dict | None (see _collision), map_collision: dict | None (see _map_collision),
-        goal: dict | None (see _goal; not part of the struct: sample / sample_step / guidance_step keep it on the handle for the call))
+        goal: dict | None (see _goal; not part of the struct: sample / sample_step / guidance_step keep it on the handle for the call),
+        social_group: dict | None (see _social; kept on the handle for the call likewise))
         -> (CldGuidance, tensors kept alive).  A `scale` is a per-agent tensor [B] (weight / (agents of the scene * 52),
         as DiffuserGuidance averages) or a scalar weight (divided by 52 here).  lr None = sigma_t; perturb_th None = no clip (what
         the reference's perturb() does), "sigma" = clip to sigma_t, a number = clip to it (include/cld.h)."""
@@ -588,6 +589,90 @@ class Engine:
         finally:
             self.lib.cld_set_goal_term(self._h, None)
 
+    def _social(self, c: Mapping, B: int):
+        """dict(groups: one list of agent indices per group (each sorted ascending here), leader: per group an agent (batch) index | -1
+        | None, social_dist = 1.5 and cohesion = 0.8: scalar or per group, scale [G] (d total / d value of a member row: weight /
+        (members x samples)), world_from_agent [A,3,3], draw_r (int32) / draw_u: both or neither, [n_iter, n_opt, B, 52] (or [B, 52]
+        for one evaluation), seed = 0, iter_base = 0, num_samp = 1, max_members: default the largest group)
+        -> (CldSocialGroup, tensors kept alive): upstream's SocialGroupLoss (src/tbsim/utils/guidance_loss.py:1137-1207) over all
+        groups of the batch.  B = A * num_samp."""
+        N = int(c.get("num_samp", 1))
+        if N < 1 or B % N:
+            raise CldError(f"social_group: {B} rows are not a multiple of num_samp = {N}")
+        A = B // N
+        missing = [k for k in ("groups", "scale", "world_from_agent") if c.get(k) is None]
+        if missing:
+            raise CldError(f"social_group: missing {missing}")
+        groups = [sorted(int(a) for a in torch.as_tensor(g).reshape(-1).tolist()) for g in c["groups"]]
+        G = len(groups)
+        flat = [a for g in groups for a in g]
+        if G < 1 or not flat or min(flat) < 0 or max(flat) >= A:
+            raise CldError(f"social_group: groups must name agents 0..{A - 1}")
+        if len(set(flat)) != len(flat):
+            raise CldError("social_group: an agent is in two groups")
+        start = torch.tensor(np.concatenate([[0], np.cumsum([len(g) for g in groups])]), dtype=torch.int32, device=self.device)
+        member = torch.tensor(flat, dtype=torch.int32, device=self.device)
+        ld = c.get("leader")
+        ld = [-1] * G if ld is None else [-1 if v is None else int(v) for v in (ld if isinstance(ld, (list, tuple)) else torch.as_tensor(ld).reshape(-1).tolist())]
+        if len(ld) != G:
+            raise CldError(f"social_group leader: expected {G} entries, got {len(ld)}")
+        leader = torch.tensor(ld, dtype=torch.int32, device=self.device)
+
+        def per_group(key, default):
+            v = c.get(key, default)
+            return torch.full((G,), float(v), device=self.device) if np.isscalar(v) else self._f32(torch.as_tensor(v, dtype=torch.float32), (G,))
+        sd, coh = per_group("social_dist", 1.5), per_group("cohesion", 0.8)
+        sc = self._f32(torch.as_tensor(c["scale"], dtype=torch.float32), (G,))
+        wfa = self._f32(c["world_from_agent"], (A, 3, 3))
+        dr = du = None
+        n_iter = n_opt = 0
+        if (c.get("draw_r") is None) != (c.get("draw_u") is None):
+            raise CldError("social_group: draw_r and draw_u go together (both or neither)")
+        if c.get("draw_r") is not None:
+            dr = torch.as_tensor(c["draw_r"]).to(self.device, torch.int32)
+            du = self._f32(c["draw_u"])
+            if dr.dim() == 2:
+                dr, du = dr[None, None], du[None, None]
+            if dr.dim() != 4 or tuple(dr.shape[2:]) != (B, T) or dr.shape != du.shape:
+                raise CldError(f"social_group: draw_r / draw_u must be [n_iter, n_opt, {B}, {T}], got {tuple(dr.shape)} / {tuple(du.shape)}")
+            dr, du = dr.contiguous(), du.contiguous()
+            n_iter, n_opt = int(dr.shape[0]), int(dr.shape[1])
+        cs = _lib.CldSocialGroup(start.data_ptr(), member.data_ptr(), leader.data_ptr(), sd.data_ptr(), coh.data_ptr(), sc.data_ptr(),
+                                 wfa.data_ptr(), None if dr is None else dr.data_ptr(), None if du is None else du.data_ptr(),
+                                 int(c.get("seed", 0)) & 0xFFFFFFFFFFFFFFFF, G, N, int(c.get("max_members") or max(len(g) for g in groups)),
+                                 int(c.get("iter_base", 0)), n_iter, n_opt)
+        return cs, (start, member, leader, sd, coh, sc, wfa, dr, du)
+
+    @contextlib.contextmanager
+    def _social_term(self, guidance: Optional[Mapping], B: int):
+        """The `social_group` entry of a guidance dict kept on the handle for the library call inside (cld_set_social_term), and
+        cleared behind it whatever happens: no term outlives the call that set it."""
+        g = None if guidance is None else guidance.get("social_group")
+        if g is None:
+            yield
+            return
+        cs, keep = self._social(g, B)
+        self._check(self.lib.cld_set_social_term(self._h, C.byref(cs)), "cld_set_social_term")
+        try:
+            yield
+        finally:
+            self.lib.cld_set_social_term(self._h, None)
+
+    def social_group_loss(self, traj, term: Mapping, grad_in=None, want_grad=True):
+        """Upstream's SocialGroupLoss on decoded plans [B,52,6] (descaled, sample-minor rows; `term`: see _social) -> (per-row values
+        [B], 0 outside the groups, grad_in + d total / d traj [B,52,6]); cld_social_group_loss.  Caller draws: slab [0, 0]."""
+        traj = self._f32(traj)
+        B = traj.shape[0]
+        traj = self._f32(traj, (B, T, 6))
+        cs, keep = self._social(term, B)
+        gi = None if grad_in is None else self._f32(grad_in, (B, T, 6))
+        loss = torch.empty(B, dtype=torch.float32, device=self.device)
+        grad = torch.empty(B, T, 6, dtype=torch.float32, device=self.device) if want_grad else None
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cld_social_group_loss(self._h, _ptr(traj), C.byref(cs), _ptr(gi), _ptr(loss), _ptr(grad), B, self._stream()),
+                        "cld_social_group_loss")
+        return (loss, grad) if want_grad else loss
+
     def goal_loss(self, traj, goal: Mapping, grad_in=None, want_grad=True):
         """Upstream's global waypoint losses on decoded plans [B,52,6] (descaled, sample-minor rows; `goal`: see _goal) ->
         (per-row values [B] as upstream files them under guide_losses, grad_in + scale * d value / d traj [B,52,6]); cld_goal_loss."""
@@ -660,7 +745,7 @@ class Engine:
         xn = torch.empty_like(mean) if z is not None else None
         gr = torch.empty_like(mean) if want_grad else None
         ws, wsn = self._workspace(B)
-        with torch.cuda.device(self.device), self._goal_term(guidance, B), self._map_source_term((guidance or {}).get("map_collision"), B):
+        with torch.cuda.device(self.device), self._goal_term(guidance, B), self._social_term(guidance, B), self._map_source_term((guidance or {}).get("map_collision"), B):
             self._check(self.lib.cld_guidance_step(self._h, _ptr(mean), _ptr(cond), C.byref(cg), C.c_float(sigma), _ptr(z),
                                                    _ptr(mg), _ptr(xn), _ptr(gr), B, ws, wsn, self._stream()), "cld_guidance_step")
         out = (mg,) + ((xn,) if z is not None else ()) + ((gr,) if want_grad else ())
@@ -721,7 +806,7 @@ class Engine:
         x1 = torch.empty_like(x_T) if (want_x1 and 1 in range(0, self.n_timesteps, self.stride)) else None
         logp = torch.empty(B, dtype=torch.float32, device=self.device) if want_logp else None
         cfg = non_cond is not None and guidance_w != 0.0
-        with torch.cuda.device(self.device), self._goal_term(guidance, B), self._map_source_term((guidance or {}).get("map_collision"), B):
+        with torch.cuda.device(self.device), self._goal_term(guidance, B), self._social_term(guidance, B), self._map_source_term((guidance or {}).get("map_collision"), B):
             if guidance is not None:
                 cg, keep = self._guidance(guidance, B)
                 non_cond = self._f32(non_cond, (B, COND)) if cfg else None
@@ -761,7 +846,7 @@ class Engine:
         gr = torch.empty_like(x_t) if guided and want_grad else None
         ws, wsn = self._workspace(2 * ((B + 15) // 16 * 16) if cfg else B)
         sigma = C.c_float()
-        with torch.cuda.device(self.device), self._goal_term(guidance, B), self._map_source_term((guidance or {}).get("map_collision"), B):
+        with torch.cuda.device(self.device), self._goal_term(guidance, B), self._social_term(guidance, B), self._map_source_term((guidance or {}).get("map_collision"), B):
             self._check(self.lib.cld_sample_step(self._h, _ptr(x_t), _ptr(cond), _ptr(non_cond), C.c_float(guidance_w),
                                                  None if cg is None else C.byref(cg), int(t_idx), _ptr(z), _ptr(xn), _ptr(mean),
                                                  _ptr(mg), _ptr(gr), C.byref(sigma), B, ws, wsn, self._stream()), "cld_sample_step")

@@ -186,6 +186,14 @@ def refresh_collision_terms(g: Optional[Mapping], obs: Mapping, world=None):
     return out
 
 
+def refresh_social_term(g: Optional[Mapping], obs: Mapping):
+    """The guidance dict `g` with the frames of its social-group term taken from `obs` where it holds them (upstream's loss reads
+    data_batch['world_from_agent'] at every call, guidance_loss.py:1156); nothing is modified in place."""
+    if g is None or g.get("social_group") is None or obs.get("world_from_agent") is None:
+        return g
+    return dict(g, social_group=dict(g["social_group"], world_from_agent=obs["world_from_agent"]))
+
+
 class CldPolicy:
     def __init__(self, dm: DmModel, vae: VaeModel, context_encoder: Optional[Callable] = None,
                  disable_control_on_stationary: bool = False, moving_speed_th: float = 0.5, select_per_scene: bool = False):
@@ -202,6 +210,7 @@ class CldPolicy:
         self.goal_reached = None
         self.goal_global_t = None
         self.goal_reached_by = "any"
+        self.social_iter = 0                          # evaluation index of the next plan's first loop iteration (social-group draws)
 
     def eval(self):
         return self
@@ -214,14 +223,23 @@ class CldPolicy:
         every get_action, as upstream's losses read data_batch at every call (refresh_collision_terms); False (the default): they keep
         what `data_batch` held here -- frozen frames.  `map_source` (dict: maps, scene_map, map_from_world, world, raster settings;
         SceneObserver.map_source()): map_collision reads the scene maps instead of a per-agent drivable raster, and `data_batch` needs
-        only extent (and curr_speed) for it."""
+        only extent (and curr_speed) for it.  `social_group` configs (guidance_loss.py:1137-1207) are taken out first
+        (social_groups_from_config; `data_batch` needs world_from_agent) and kept as guidance['social_group']; with
+        follow_observation their frames follow every observation too.  `social_seed` seeds their draws (default 0); every
+        get_action moves their evaluation index on, so successive plans do not reuse draws."""
         data_batch = opt.pop("data_batch", None)         # observation fields scene-coupled losses read (agent_collision: extent, world_from_agent, curr_speed)
         follow = bool(opt.pop("follow_observation", False))
         map_source = opt.pop("map_source", None)
         by = opt.pop("goal_reached_by", "any")
         if by not in ("any", "own"):
             raise ValueError(f"goal_reached_by={by!r} (any | own)")
-        self._guidance = dict(guidance_from_config(guidance_config_list, scene_index, data_batch=data_batch, map_source=map_source), **opt)
+        social_seed = int(opt.pop("social_seed", 0))
+        rest, social = social_groups_from_config(guidance_config_list, scene_index, data_batch)
+        base = guidance_from_config(rest, scene_index, data_batch=data_batch, map_source=map_source) if social is None or any(len(c) for c in rest) else {}
+        if social is not None:
+            base["social_group"] = dict(social, seed=social_seed)
+        self._guidance = dict(base, **opt)
+        self.social_iter = 0
         self._follow_observation = follow
         self._guidance_cfg = (guidance_config_list, torch.as_tensor(scene_index).reshape(-1).cpu())
         # a new configuration starts with nobody arrived (upstream builds new loss objects: have_reached_mask = None)
@@ -265,7 +283,9 @@ class CldPolicy:
         vals = (self.vae.engine.guidance_losses(traj.reshape(B * N, 52, 6), g).reshape(B, N, 4) if has_builtin
                 else torch.full((B, N, 4), float("nan"), device=traj.device))
         nan = torch.full((B, N), float("nan"), device=vals.device)
-        colv = mapv = goalv = None
+        colv = mapv = goalv = socv = None
+        if g.get("social_group") is not None:        # unweighted per-row values (guidance_loss.py:1205); 0 outside the groups here, NaN below
+            socv = self.vae.engine.social_group_loss(traj.reshape(B * N, 52, 6), dict(g["social_group"], num_samp=N), want_grad=False).reshape(B, N)
         if g.get("goal") is not None:                # unweighted per-row values, 0 for agents that have arrived (guidance_loss.py:1029,1133)
             goalv = self.vae.engine.goal_loss(traj.reshape(B * N, 52, 6), dict(g["goal"], num_samp=N), want_grad=False).reshape(B, N)
         if g.get("agent_collision") is not None:     # per-agent values as upstream files them (unweighted; :2166-2168)
@@ -285,7 +305,7 @@ class CldPolicy:
                     mask[idx] = True
                     mask = mask.to(vals.device)
                     v = (colv if c["name"] == "agent_collision" else mapv if c["name"] == "map_collision" else
-                         goalv if c["name"] in GOAL_KINDS else vals[..., LOSS_COLUMN[c["name"]]])
+                         goalv if c["name"] in GOAL_KINDS else socv if c["name"] == "social_group" else vals[..., LOSS_COLUMN[c["name"]]])
                     out["%s_scene_%03d_%02d" % (c["name"], si, gi)] = torch.where(mask[:, None], v, nan)
         else:       # a plain `guidance=` dict: one scene, one entry per active term
             names.append([])
@@ -305,6 +325,12 @@ class CldPolicy:
                     if bool((kind == k).any()):
                         out["%s_scene_000_%02d" % (nm, len(names[0]))] = torch.where((kind == k)[:, None], goalv, nan)
                         names[0].append(nm)
+            if socv is not None:
+                inside = torch.zeros(B, dtype=torch.bool)
+                for grp in g["social_group"]["groups"]:
+                    inside[torch.as_tensor(grp, dtype=torch.long)] = True
+                out["social_group_scene_000_%02d" % len(names[0])] = torch.where(inside.to(socv.device)[:, None], socv, nan)
+                names[0].append("social_group")
         return out, names
 
     @torch.no_grad()
@@ -345,7 +371,12 @@ class CldPolicy:
             g = dict(g, guide_clean=True)
         from_cfg = g is self._guidance and self._guidance_cfg is not None
         if guidance is None and self._follow_observation:           # the collision terms of set_guidance follow this observation
-            g = refresh_collision_terms(g, obs_dict)
+            g = refresh_social_term(refresh_collision_terms(g, obs_dict), obs_dict)
+        if g is not None and g.get("social_group") is not None and guidance is None:
+            # the plan's loop iterations take evaluation indices social_iter .. social_iter + loop_steps - 1, the values reported on the
+            # final output (below) the one behind them
+            g = dict(g, social_group=dict(g["social_group"], iter_base=self.social_iter))
+            self.social_iter += eng.loop_steps + 1
         if g is not None and g.get("goal") is not None:
             carry = guidance is None
             g = dict(g, goal=self._goal_for_step(g["goal"], obs_dict, step_index, carry))
@@ -361,6 +392,9 @@ class CldPolicy:
             act_idx = choose_action_from_gt(pos, obs_dict["target_positions"], obs_dict["target_availabilities"])
         elif g is not None:
             g_rep = repeat_guidance({k: v for k, v in g.items() if k != "curr_states"}, N, a["curr_states"])
+            if g_rep.get("social_group") is not None:
+                sg = g_rep["social_group"]
+                g_rep["social_group"] = dict(sg, iter_base=int(sg.get("iter_base", 0)) + eng.loop_steps)
             losses, names = self._guide_losses(traj, g_rep, B, N, from_cfg)
             scene_of_agent = None
             if self.select_per_scene and from_cfg:
@@ -405,8 +439,8 @@ def closed_loop_rollout(policy: CldPolicy, cond_fn: Callable, centroid, yaw, cur
     of the previous plan taken into the new agent frame (the last one is the agent's position now), on the first step the current
     position repeated.  `step_index` = the sim step is the goal losses' global_t.
     With collision guidance that follows the observation (`set_guidance(..., follow_observation=True)`) the same holds for
-    `world_from_agent` (from the world pose), `curr_speed` (`curr_states[:, 2]`) and `world` [B,3], the pose itself, which a
-    map_collision term in map mode is evaluated at; a raster-mode term needs `drivable_map` from `cond_fn` (SceneObserver gives it).
+    `world_from_agent` (from the world pose; a social-group term reads it too), `curr_speed` (`curr_states[:, 2]`) and `world`
+    [B,3], the pose itself, which a map_collision term in map mode is evaluated at; a raster-mode term needs `drivable_map` from `cond_fn` (SceneObserver gives it).
     Returns the world poses after each sim step [n_sim_steps, B, 3]."""
     import inspect
     from contextlib import nullcontext
@@ -441,7 +475,7 @@ def closed_loop_rollout(policy: CldPolicy, cond_fn: Callable, centroid, yaw, cur
                         hw = world[:, None, :2].expand(-1, n_step_action, -1) if hist_world is None else hist_world
                         obs["agent_hist"] = transform_points(hw, torch.as_tensor(obs["agent_from_world"]).float().to(hw.device))
                 pg = policy._guidance or {}
-                if gk is None and policy._follow_observation and (pg.get("agent_collision") is not None or pg.get("map_collision") is not None):
+                if gk is None and policy._follow_observation and any(pg.get(k) is not None for k in ("agent_collision", "map_collision", "social_group")):
                     obs = dict(obs)                   # the collision terms follow the observation: what cond_fn's lacks, from the loop's own state
                     if "world_from_agent" not in obs:
                         obs["world_from_agent"] = frames_from_pose(world)
@@ -468,6 +502,52 @@ def closed_loop_rollout(policy: CldPolicy, cond_fn: Callable, centroid, yaw, cur
     return torch.stack(poses)
 
 
+def social_groups_from_config(guidance_config_list, scene_index, data_batch: Optional[Mapping] = None):
+    """Upstream's `social_group` configs (SocialGroupLoss, guidance_loss.py:1137-1207) taken out of a guidance configuration ->
+    (the list without them, the `social_group` entry of a guidance dict -- Engine._social -- or None when there is none).
+
+    One group per config: the config's `agents` (local indices into its scene) or the whole scene; params leader_idx = 0,
+    social_dist = 1.5, cohesion = 0.8.  `leader_idx` is compared with the agents' BATCH indices, as upstream's code does (its
+    docstring says "index in the scene"); one that names no member detaches nobody.  scale = weight / members, as for the goal
+    losses.  ValueError:
+    no world_from_agent in `data_batch`, a group of fewer than 2 members (upstream cannot run it: randint(0, 0)), an agent in two
+    groups, cohesion outside [0, 1]."""
+    scene_index = torch.as_tensor(scene_index).reshape(-1).cpu()
+    _, local = torch.unique_consecutive(scene_index, return_inverse=True)
+    rest, term = [], None
+    taken = torch.zeros(scene_index.numel(), dtype=torch.bool)
+    for si, cfgs in enumerate(guidance_config_list):
+        keep = []
+        for gi, cfg in enumerate(cfgs):
+            if cfg["name"] != "social_group":
+                keep.append(cfg)
+                continue
+            if data_batch is None or data_batch.get("world_from_agent") is None:
+                raise ValueError("social_group needs data_batch with world_from_agent")
+            members = torch.nonzero(local == si).reshape(-1)
+            agents = cfg.get("agents")
+            idx = members if agents is None else members[torch.as_tensor(agents, dtype=torch.long)]
+            idx = torch.sort(idx)[0]
+            if idx.numel() < 2:
+                raise ValueError(f"social_group: a group needs at least 2 members, scene {si} config {gi} has {idx.numel()}")
+            if idx.unique().numel() != idx.numel() or bool(taken[idx].any()):
+                raise ValueError("social_group: an agent is in two groups")
+            taken[idx] = True
+            prm = cfg.get("params") or {}
+            coh = float(prm.get("cohesion", 0.8))
+            if not 0.0 <= coh <= 1.0:
+                raise ValueError(f"social_group: cohesion {coh} outside [0, 1]")
+            if term is None:
+                term = dict(groups=[], leader=[], social_dist=[], cohesion=[], scale=[], world_from_agent=data_batch["world_from_agent"])
+            term["groups"].append(idx.tolist())
+            term["leader"].append(int(prm.get("leader_idx", 0)))
+            term["social_dist"].append(float(prm.get("social_dist", 1.5)))
+            term["cohesion"].append(coh)
+            term["scale"].append(float(cfg["weight"]) / idx.numel())
+        rest.append(keep)
+    return rest, term
+
+
 def guidance_from_config(guidance_config_list, scene_index, horizon: int = 52, data_batch: Optional[Mapping] = None,
                          map_source: Optional[Mapping] = None) -> dict:
     """Upstream's guidance configuration -> the `guidance=` dict of `DmModel.forward` / `Engine.sample`.
@@ -485,7 +565,9 @@ def guidance_from_config(guidance_config_list, scene_index, horizon: int = 52, d
     waypoint losses global_target_pos / global_target_pos_at_time (:930-1135; params target_pos, target_time, urgency, pref_speed = 1.42,
     dt = 0.1, min_progress_dist = 0.5, target_tolerance = None / 2, action_num = 5, all indexed by the config's `agents`; scale =
     weight / agents; at most one per agent, one dt and one min_progress_dist per call); at most
-    one of each other loss per scene, one parameter set per call; the others (social groups, stop signs, lane keeping, ...) are not built.  One speed / acceleration limit value per call."""
+    one of each other loss per scene, one parameter set per call; the others (stop signs, lane keeping, ...) are not built, and
+    `social_group` is refused HERE too: it is scene-coupled and random, and enters one level up (social_groups_from_config, which
+    CldPolicy.set_guidance calls first).  One speed / acceleration limit value per call."""
     scene_index = torch.as_tensor(scene_index).reshape(-1).cpu()
     B = scene_index.numel()
     _, local = torch.unique_consecutive(scene_index, return_inverse=True)

@@ -356,6 +356,61 @@ int cld_goal_loss(cld_handle h, const float* traj, const cld_goal* g, const floa
  * pointer in cld_guidance: that struct's layout is frozen.) */
 int cld_set_goal_term(cld_handle h, const cld_goal* g);
 
+/* Upstream's SocialGroupLoss (`social_group`, src/tbsim/utils/guidance_loss.py:1137-1207): the members of a group keep social_dist
+ * to one another.  Group g holds the agents member[group_start[g] .. group_start[g + 1]) (ascending; M of them, an agent in at most
+ * one group).  For every sample n and step t the members' positions go to the world frame (world_from_agent[a] (x, y)) and member i
+ * (its position in the group) is paired with
+ *     nb(i) = u < cohesion[g] ? (r < i ? r : r + 1) : argmin_{j != i} |p_i - p_j|      (lowest j on a tie)
+ * where (r, u) is the draw of (row of the member's plan, t) in this evaluation: r uniform in [0, M - 2], u uniform in [0, 1), compared
+ * in fp32.  value[i, n] = mean_t (|p_i - p_nb(i)| - social_dist[g])^2; the term's total is sum over member rows of scale[g] * value
+ * (scale = d total / d value of a member row: weight / (M * samples) reproduces upstream's weight * mean over [M, N]).
+ * The LEADER is the member whose agent index equals leader[g] (-1, or an index that names no member: nobody).  Upstream's docstring
+ * calls leader_idx "the index in the scene", but its code compares it with the BATCH index of the agent (:1159-1170); the code is
+ * followed here, so leader[] holds batch (agent) indices.  The leader's position is detached: it receives no gradient, neither for
+ * its own term nor as somebody's neighbour; its value still counts, and its neighbour receives the gradient of the leader's term.
+ * Every other pair term sends its gradient to both ends; the norm's gradient at distance 0 is 0; only the x, y columns receive
+ * anything (rotated back by R_a^T).  Distances are differences of positions formed directly in fp32 (no matrix-product form).
+ * Draws: draw_r / draw_u, both given or both NULL.  Given: DEVICE [n_iter, n_opt, B, 52] over ALL plan rows (sample-minor; rows of
+ * non-members are ignored; r is clamped to [0, M - 2]) -- evaluation (it, k) of a guided call reads slab [it, k]: it = the loop
+ * iteration of cld_sample_guided (0 in cld_sample_step / cld_guidance_step), k = the optimiser step - 1; cld_social_group_loss reads
+ * slab [0, 0].  NULL: the library's counter-based generator, keyed by (seed, a stream tag of its own -- no value is shared with the
+ * diffusion noise --, the evaluation index (iter_base + it, k), row * 52 + t); cohesion == 0 draws nothing.  A chain stepped through
+ * cld_sample_step with iter_base = 0, 1, ... therefore draws what cld_sample_guided draws with iter_base = 0.
+ * Contract on max_members (as cld_collision.max_scene_agents): the launch sizes its LDS and grid from it; a group whose device-side
+ * group_start holds MORE members -- or fewer than 2, which upstream cannot run -- is not evaluated: its members get NaN values and a
+ * gradient of grad_in (or 0).  2 <= max_members <= 128 (CLD_ERR_ARG beyond).  Rows outside every group: value 0, gradient grad_in.
+ * Deterministic: no atomics, the same bits on every run.  Agents A = B / num_samp. */
+typedef struct cld_social_group {
+    const int32_t* group_start;     /* DEVICE [num_groups + 1] offsets into member                                          */
+    const int32_t* member;          /* DEVICE [group_start[num_groups]] agent indices, ascending within a group             */
+    const int32_t* leader;          /* DEVICE [num_groups] agent (batch) index of the group's leader, or -1                 */
+    const float* social_dist;       /* DEVICE [num_groups] metres (upstream default 1.5)                                    */
+    const float* cohesion;          /* DEVICE [num_groups] in [0, 1] (0.8)                                                  */
+    const float* scale;             /* DEVICE [num_groups] d total / d value of a member row                                */
+    const float* world_from_agent;  /* DEVICE [A,3,3] row-major                                                             */
+    const int32_t* draw_r;          /* DEVICE [n_iter, n_opt, B, 52] or NULL                                                */
+    const float* draw_u;            /* DEVICE [n_iter, n_opt, B, 52] or NULL                                                */
+    uint64_t seed;                  /* generator seed (draws NULL)                                                          */
+    int32_t num_groups;
+    int32_t num_samp;
+    int32_t max_members;            /* largest group (sizes the kernel's LDS; 2..128)                                       */
+    int32_t iter_base;              /* evaluation index of the call's first loop iteration (generator only)                 */
+    int32_t n_iter;                 /* leading extents of the caller draws                                                  */
+    int32_t n_opt;
+} cld_social_group;
+
+/* The loss above on given plans: traj [B,52,6] descaled -> loss [B] = the unweighted per-row values (0 outside the groups) and
+ * grad [B,52,6] = grad_in (when given; may be grad itself) + d total / d traj.  Either output may be NULL. */
+int cld_social_group_loss(cld_handle h, const float* traj, const cld_social_group* term, const float* grad_in, float* loss,
+                          float* grad, int32_t B, void* stream);
+
+/* Keep a social-group term on the handle (the struct is copied by value; NULL clears it).  While one is set, every guided call
+ * (cld_sample_guided, cld_sample_step, cld_guidance_step) decodes the current iterate at every optimiser step and adds the term's
+ * gradient after the goal term's; it counts as a loss term of the `cld_guidance` it is used with.  Caller draws that do not cover
+ * the call -- n_iter < its loop iterations (1 for the two step calls) or n_opt < max(grad_steps, final_grad_steps, 1) -- are
+ * CLD_ERR_ARG, decided before anything is launched.  (A setter and not a pointer in cld_guidance: that struct's layout is frozen.) */
+int cld_set_social_term(cld_handle h, const cld_social_group* term);
+
 /* cld_sample (non_cond == NULL) / cld_sample_cfg (non_cond != NULL) with the guidance step above inside the loop. */
 int cld_sample_guided(cld_handle h, const float* x_T, const float* noise, const float* cond, const float* non_cond,
                       float guidance_w, const cld_guidance* guidance, int32_t steps, float* x0, float* x1, float* logp,
