@@ -112,6 +112,18 @@ class CldSocialGroup(C.Structure):
 SOCIAL_MAX_MEMBERS = 128               # include/cld.h: the bound on cld_social_group.max_members
 
 
+class CldPairTerm(C.Structure):
+    """include/cld.h `cld_pair_term` (upstream's pair-relation losses over all pairs of a batch, device pointers)."""
+    _fields_ = [("target", C.c_void_p), ("ref", C.c_void_p), ("kind", C.c_void_p), ("lo", C.c_void_p), ("hi", C.c_void_p),
+                ("decay", C.c_void_p), ("scale", C.c_void_p), ("world_from_agent", C.c_void_p), ("agent_from_world", C.c_void_p),
+                ("agent_start", C.c_void_p), ("agent_id", C.c_void_p), ("incidence", C.c_void_p), ("num_pairs", C.c_int32),
+                ("num_samp", C.c_int32), ("num_involved", C.c_int32), ("num_incidences", C.c_int32)]
+
+
+# include/cld.h CLD_PAIR_*: the relation a pair term evaluates
+PAIR_KINDS = {"keep_distance": 0, "collision": 1, "stay_away": 2, "front_collision": 3, "collide_left": 4}
+
+
 class CldRaster(C.Structure):
     """include/cld.h `cld_raster` (the scene an observation raster is built from, device pointers)."""
     _fields_ = [("hist_world", C.c_void_p), ("hist_avail", C.c_void_p), ("scene_start", C.c_void_p), ("maps", C.c_void_p),
@@ -207,6 +219,8 @@ SIGNATURES = {
     "cld_set_goal_term": (C.c_int, [_P, C.POINTER(CldGoal)]),
     "cld_social_group_loss": (C.c_int, [_P, _P, C.POINTER(CldSocialGroup), _P, _P, _P, C.c_int32, _P]),
     "cld_set_social_term": (C.c_int, [_P, C.POINTER(CldSocialGroup)]),
+    "cld_pair_loss": (C.c_int, [_P, _P, C.POINTER(CldPairTerm), _P, _P, _P, C.c_int32, _P]),
+    "cld_set_pair_term": (C.c_int, [_P, C.POINTER(CldPairTerm)]),
     "cld_set_map_source": (C.c_int, [_P, C.POINTER(CldMapSource)]),
     "cld_world_step": (C.c_int, [_P, _P, _P, _P, C.c_int32, _P, _P, C.c_int32, _P]),
     "cld_rasterize": (C.c_int, [_P, C.POINTER(CldRaster), C.c_int32, C.c_int32, _P, _P, _P, _P]),

@@ -56,6 +56,8 @@ struct cld_handle_s {
     bool has_goal = false;
     cld_social_group social{};                       // cld_set_social_term: the social-group term every guided call adds while has_social
     bool has_social = false;
+    cld_pair_term pair{};                            // cld_set_pair_term: the pair-relation term every guided call adds while has_pair
+    bool has_pair = false;
     cld_map_source map_source{};                     // cld_set_map_source: what a cld_map_collision without a drivable_map reads while has_map_source
     bool has_map_source = false;
     std::vector<void*> dev_allocs;
@@ -1540,9 +1542,31 @@ static SocialArgs social_args(const cld_social_group* t, const float* traj, floa
     return a;
 }
 
+static int check_pair(cld_handle h, const char* fn, const cld_pair_term* t, int B) {
+    if (!t->target || !t->ref || !t->kind || !t->lo || !t->hi || !t->decay || !t->scale || !t->world_from_agent || !t->agent_start || !t->agent_id || !t->incidence)
+        return fail(h, CLD_ERR_ARG, std::string(fn) + ": pair term: null pointer");
+    if (t->num_pairs < 1 || t->num_samp < 1 || B % t->num_samp)
+        return fail(h, CLD_ERR_ARG, std::string(fn) + ": pair term: B must be agents x num_samp, num_pairs >= 1");
+    // an agent is listed once and a pair has two ends: at most 2 num_pairs involved agents and incidences
+    if (t->num_involved < 0 || t->num_incidences < 0 || t->num_involved > B / t->num_samp || (int64_t)t->num_involved > 2 * (int64_t)t->num_pairs ||
+        (int64_t)t->num_incidences > 2 * (int64_t)t->num_pairs)
+        return fail(h, CLD_ERR_ARG, std::string(fn) + ": pair term: num_involved / num_incidences exceed what num_pairs pairs of the batch's agents can give");
+    if ((int64_t)t->num_pairs * t->num_samp > INT32_MAX / 64 || (int64_t)t->num_involved * t->num_samp * 52 > INT32_MAX)
+        return fail(h, CLD_ERR_ARG, std::string(fn) + ": pair term: too many pairs for one launch");
+    return CLD_OK;
+}
+static PairArgs pair_args(const cld_pair_term* t, const float* traj, float* value, float* grad, int B) {
+    PairArgs a{};
+    a.traj = traj; a.world_from_agent = t->world_from_agent; a.agent_from_world = t->agent_from_world; a.target = t->target; a.ref = t->ref;
+    a.kind = t->kind; a.lo = t->lo; a.hi = t->hi; a.decay = t->decay; a.scale = t->scale; a.agent_start = t->agent_start; a.agent_id = t->agent_id;
+    a.incidence = t->incidence; a.value = value; a.grad = grad; a.rows = B; a.num_pairs = t->num_pairs; a.num_samp = t->num_samp;
+    a.num_involved = t->num_involved; a.num_incidences = t->num_incidences;
+    return a;
+}
+
 static int check_guidance(cld_handle h, const char* fn, const cld_guidance* gd, int B, int iters = 1) {
     if (!h->has_decoder) return fail(h, CLD_ERR_STATE, std::string(fn) + ": guidance needs the decoder weights");
-    if (!gd->curr_states || (!gd->target_speed && !gd->speed_limit_scale && !gd->acc_limit_scale && !gd->target_pos_scale && !gd->ext_grad && !gd->collision && !gd->map_collision && !h->has_goal && !h->has_social))
+    if (!gd->curr_states || (!gd->target_speed && !gd->speed_limit_scale && !gd->acc_limit_scale && !gd->target_pos_scale && !gd->ext_grad && !gd->collision && !gd->map_collision && !h->has_goal && !h->has_social && !h->has_pair))
         return fail(h, CLD_ERR_ARG, std::string(fn) + ": guidance needs curr_states and at least one loss term");
     if (gd->collision) {
         const int rcc = check_collision(h, fn, gd->collision, B);
@@ -1560,6 +1584,10 @@ static int check_guidance(cld_handle h, const char* fn, const cld_guidance* gd, 
         return fail(h, CLD_ERR_ARG, std::string(fn) + ": grad_steps out of range (0..64)");
     if (h->has_social) {
         const int rcc = check_social(h, fn, &h->social, B, iters, std::max(gd->grad_steps, gd->final_grad_steps));
+        if (rcc) return rcc;
+    }
+    if (h->has_pair) {
+        const int rcc = check_pair(h, fn, &h->pair, B);
         if (rcc) return rcc;
     }
     if (gd->optimizer != CLD_GUIDE_ADAM && gd->optimizer != CLD_GUIDE_SGD) return fail(h, CLD_ERR_ARG, std::string(fn) + ": unknown optimizer");
@@ -1594,7 +1622,7 @@ static int run_guidance(cld_handle h, const Ws& w, const cld_guidance* gd, int B
         const bool last = k == steps;
         g.opt_step = k;
         g.mean = k == 1 ? mean0 : w.gcur;
-        if (gd->collision || gd->map_collision || h->has_goal || h->has_social) {    // the scene / map / goal / social terms are functions of the decoded plans of the current iterate
+        if (gd->collision || gd->map_collision || h->has_goal || h->has_social || h->has_pair) {    // the scene / map / goal / social / pair terms are functions of the decoded plans of the current iterate
             if (B >= 256 && guide_forward_available(B, h->force_kernel[CLD_KERNEL_GUIDE]) && h->force_kernel[CLD_KERNEL_DECODE] == FORM_AUTO) {
                 // (from the batch size at which cld_decode itself would take its 16-agent MFMA form, ~0.3 ms; below that the
                 //  one-agent-per-workgroup decoder is the shorter chain: 64 agents 579 vs 616 us per collision-guided step)
@@ -1632,6 +1660,11 @@ static int run_guidance(cld_handle h, const Ws& w, const cld_guidance* gd, int B
         if (h->has_social) {                         // after the goal term's: evaluation (loop iteration, optimiser step) picks the draws
             const float* gin = (gd->collision || gd->map_collision || h->has_goal) ? w.col_grad : gd->ext_grad;
             HIPCK(h, launch_social_group(social_args(&h->social, w.col_traj, nullptr, w.col_grad, B, (int)salt, k - 1), gin, s));
+            g.ext_grad = w.col_grad;
+        }
+        if (h->has_pair) {                           // after the social term's, on the same decoded iterate
+            const float* gin = (gd->collision || gd->map_collision || h->has_goal || h->has_social) ? w.col_grad : gd->ext_grad;
+            HIPCK(h, launch_pair(pair_args(&h->pair, w.col_traj, nullptr, w.col_grad, B), gin, s));
             g.ext_grad = w.col_grad;
         }
         g.z = last ? z : nullptr;
@@ -2082,6 +2115,23 @@ int cld_set_social_term(cld_handle h, const cld_social_group* term) {
     if (!h) return CLD_ERR_ARG;
     h->has_social = term != nullptr;
     h->social = term ? *term : cld_social_group{};
+    return CLD_OK;
+}
+
+int cld_pair_loss(cld_handle h, const float* traj, const cld_pair_term* term, const float* grad_in, float* value, float* grad, int32_t B,
+                  void* stream) {
+    if (!h) return CLD_ERR_ARG;
+    if (!traj || !term || B < 1 || (!value && !grad)) return fail(h, CLD_ERR_ARG, "cld_pair_loss: bad argument");
+    int rc = check_pair(h, "cld_pair_loss", term, B);
+    if (rc) return rc;
+    HIPCK(h, launch_pair(pair_args(term, traj, value, grad, B), grad_in, static_cast<hipStream_t>(stream)));
+    return CLD_OK;
+}
+
+int cld_set_pair_term(cld_handle h, const cld_pair_term* term) {
+    if (!h) return CLD_ERR_ARG;
+    h->has_pair = term != nullptr;
+    h->pair = term ? *term : cld_pair_term{};
     return CLD_OK;
 }
 

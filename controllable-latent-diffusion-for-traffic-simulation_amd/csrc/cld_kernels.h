@@ -582,6 +582,29 @@ struct SocialArgs {
 // grad = grad_in (or 0) + the term's gradient; grad_in may be grad itself
 hipError_t launch_social_group(const SocialArgs& a, const float* grad_in, hipStream_t s);
 
+// upstream's pair-relation losses + their gradient w.r.t. the decoded plans (pair_kernels.hip; guidance_loss.py:1631-1791, 1844-1956, 2014-2082)
+enum { PAIR_KEEP_DISTANCE = 0, PAIR_COLLISION = 1, PAIR_STAY_AWAY = 2, PAIR_FRONT_COLLISION = 3, PAIR_COLLIDE_LEFT = 4 };   // cld.h CLD_PAIR_*
+struct PairArgs {
+    const float* traj;               // [rows = A * num_samp, 52, 6] descaled plans, sample-minor
+    const float* world_from_agent;   // [A, 3, 3]
+    const float* agent_from_world;   // [A, 3, 3] or null: the inverse rotation of world_from_agent
+    const int* target;               // [num_pairs] agent indices
+    const int* ref;                  // [num_pairs]
+    const int* kind;                 // [num_pairs] PAIR_*
+    const float* lo;                 // [num_pairs] min distance / collision radius
+    const float* hi;                 // [num_pairs] max distance
+    const float* decay;              // [num_pairs] <= 0: a plain mean over the steps
+    const float* scale;              // [num_pairs] d total / d value of a (pair, sample)
+    const int* agent_start;          // [num_involved + 1] offsets into incidence
+    const int* agent_id;             // [num_involved] the agents that sit in a pair, each once
+    const int* incidence;            // [num_incidences] pair * 2 + role (0 target, 1 ref), ascending per agent
+    float* value;                    // [num_pairs, num_samp] or null
+    float* grad;                     // [rows, 52, 6] or null; the kernel ADDS to it (launch_pair puts grad_in there first)
+    int rows, num_pairs, num_samp, num_involved, num_incidences;
+};
+// grad = grad_in (or 0) + the term's gradient; grad_in may be grad itself
+hipError_t launch_pair(const PairArgs& a, const float* grad_in, hipStream_t s);
+
 // PPO reward (models/rl/criticmodel.py:7-64)
 struct RewardArgs {
     const float* traj;                // [B,52,6] descaled (x, y, v, yaw, acc, yaw-rate), agent frame

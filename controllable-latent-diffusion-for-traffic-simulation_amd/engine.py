@@ -50,6 +50,23 @@ def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+def pair_incidences(target, ref, A: int):
+    """The gather lists of a pair term (include/cld.h `cld_pair_term`): -> (agent_id: the agents 0..A-1 that sit in a pair, ascending,
+    agent_start: offsets [len(agent_id) + 1], incidence: per agent its pair * 2 + role (0 = target, 1 = ref) in ascending order).
+    An end outside 0..A-1 is listed nowhere."""
+    per = {}
+    for p, (i, j) in enumerate(zip(target, ref)):
+        for role, a in enumerate((int(i), int(j))):
+            if 0 <= a < A:
+                per.setdefault(a, []).append(2 * p + role)
+    ids = sorted(per)
+    start, inc = [0], []
+    for a in ids:
+        inc += sorted(per[a])
+        start.append(len(inc))
+    return ids, start, inc
+
+
 def _param_table(lib, h, model):
     lib = lib or _lib.load()
     count, info, floats = (getattr(lib, f"cld_{model}_param_{s}") for s in ("count", "info", "floats"))
@@ -332,7 +349,7 @@ class Engine:
         acc_limit (limit, scale) | None, target_pos (pos [B,2], time index [B], scale) | None, lr | None, perturb_th | None | "sigma", optimizer "adam" | "sgd",
         grad_steps = 1, guide_clean = False, agent_collision: dict | None (see _collision), map_collision: dict | None (see _map_collision),
         goal: dict | None (see _goal; not part of the struct: sample / sample_step / guidance_step keep it on the handle for the call),
-        social_group: dict | None (see _social; kept on the handle for the call likewise))
+        social_group: dict | None (see _social; kept on the handle for the call likewise), pair: dict | None (see _pair; likewise))
         -> (CldGuidance, tensors kept alive).  A `scale` is a per-agent tensor [B] (weight / (agents of the scene * 52),
         as DiffuserGuidance averages) or a scalar weight (divided by 52 here).  lr None = sigma_t; perturb_th None = no clip (what
         the reference's perturb() does), "sigma" = clip to sigma_t, a number = clip to it (include/cld.h)."""
@@ -673,6 +690,86 @@ class Engine:
                         "cld_social_group_loss")
         return (loss, grad) if want_grad else loss
 
+    def _pair(self, c: Mapping, B: int):
+        """dict(target [P], ref [P]: agent (batch) indices, kind [P]: a name or number of _lib.PAIR_KINDS (scalar or per pair), lo = 0
+        (min distance / collision radius), hi = 0 (max distance), decay = 0 (<= 0: a plain mean over the steps): scalar or per pair,
+        scale [P] (d total / d value of a (pair, sample)) or weight [P] (scale = weight / num_samp, upstream's weight * mean over the
+        samples), world_from_agent [A,3,3], agent_from_world [A,3,3] | None (the inverse rotation of the former), num_samp = 1,
+        validate = True: a pair outside the batch or with target == ref is a CldError; False: it reaches the kernel, which gives it
+        a NaN value and no gradient) -> (CldPairTerm, tensors kept alive): upstream's pair-relation losses
+        (src/tbsim/utils/guidance_loss.py:1631-1791, 1844-1956, 2014-2082) over all pairs of the batch.  B = A * num_samp."""
+        N = int(c.get("num_samp", 1))
+        if N < 1 or B % N:
+            raise CldError(f"pair: {B} rows are not a multiple of num_samp = {N}")
+        A = B // N
+        missing = [k for k in ("target", "ref", "kind", "world_from_agent") if c.get(k) is None]
+        if missing or (c.get("scale") is None and c.get("weight") is None):
+            raise CldError(f"pair: missing {missing or ['scale | weight']}")
+        tg = [int(v) for v in torch.as_tensor(c["target"]).reshape(-1).tolist()]
+        rf = [int(v) for v in torch.as_tensor(c["ref"]).reshape(-1).tolist()]
+        P = len(tg)
+        if P < 1 or len(rf) != P:
+            raise CldError(f"pair: target and ref must name the same number (>= 1) of pairs, got {P} / {len(rf)}")
+        if c.get("validate", True):
+            for p, (i, j) in enumerate(zip(tg, rf)):
+                if not (0 <= i < A and 0 <= j < A) or i == j:
+                    raise CldError(f"pair {p}: target {i} / ref {j} must be two different agents of 0..{A - 1}")
+        kd = c["kind"]
+        kd = [kd] * P if isinstance(kd, (str, int)) else list(kd.tolist() if isinstance(kd, (torch.Tensor, np.ndarray)) else kd)
+        if len(kd) != P:
+            raise CldError(f"pair kind: expected {P} entries, got {len(kd)}")
+        try:
+            kd = [_lib.PAIR_KINDS[k] if isinstance(k, str) else int(k) for k in kd]
+        except KeyError as e:
+            raise CldError(f"pair kind {e.args[0]!r}: one of {sorted(_lib.PAIR_KINDS)}") from None
+        if any(k not in _lib.PAIR_KINDS.values() for k in kd):
+            raise CldError(f"pair kind: numbers {sorted(_lib.PAIR_KINDS.values())}")
+
+        def per_pair(key, default=0.0):
+            v = c.get(key, default)
+            return torch.full((P,), float(v), device=self.device) if np.isscalar(v) else self._f32(torch.as_tensor(v, dtype=torch.float32), (P,))
+        lo, hi, dec = per_pair("lo"), per_pair("hi"), per_pair("decay")
+        sc = per_pair("scale") if c.get("scale") is not None else per_pair("weight") / N
+        wfa = self._f32(c["world_from_agent"], (A, 3, 3))
+        afw = None if c.get("agent_from_world") is None else self._f32(c["agent_from_world"], (A, 3, 3))
+        ids, start, inc = pair_incidences(tg, rf, A)
+        i32 = lambda v: torch.tensor(v, dtype=torch.int32, device=self.device)
+        tgt, reft, kind, start_t, ids_t, inc_t = i32(tg), i32(rf), i32(kd), i32(start), i32(ids if ids else [0]), i32(inc if inc else [0])
+        cs = _lib.CldPairTerm(tgt.data_ptr(), reft.data_ptr(), kind.data_ptr(), lo.data_ptr(), hi.data_ptr(), dec.data_ptr(), sc.data_ptr(),
+                              wfa.data_ptr(), None if afw is None else afw.data_ptr(), start_t.data_ptr(), ids_t.data_ptr(), inc_t.data_ptr(),
+                              P, N, len(ids), len(inc))
+        return cs, (tgt, reft, kind, lo, hi, dec, sc, wfa, afw, start_t, ids_t, inc_t)
+
+    @contextlib.contextmanager
+    def _pair_term(self, guidance: Optional[Mapping], B: int):
+        """The `pair` entry of a guidance dict kept on the handle for the library call inside (cld_set_pair_term), and cleared behind
+        it whatever happens: no term outlives the call that set it."""
+        g = None if guidance is None else guidance.get("pair")
+        if g is None:
+            yield
+            return
+        cs, keep = self._pair(g, B)
+        self._check(self.lib.cld_set_pair_term(self._h, C.byref(cs)), "cld_set_pair_term")
+        try:
+            yield
+        finally:
+            self.lib.cld_set_pair_term(self._h, None)
+
+    def pair_loss(self, traj, term: Mapping, grad_in=None, want_grad=True):
+        """Upstream's pair-relation losses on decoded plans [B,52,6] (descaled, sample-minor rows; `term`: see _pair) -> (values
+        [P, num_samp] as upstream's classes return them, grad_in + d total / d traj [B,52,6]); cld_pair_loss."""
+        traj = self._f32(traj)
+        B = traj.shape[0]
+        traj = self._f32(traj, (B, T, 6))
+        cs, keep = self._pair(term, B)
+        gi = None if grad_in is None else self._f32(grad_in, (B, T, 6))
+        value = torch.empty(cs.num_pairs, cs.num_samp, dtype=torch.float32, device=self.device)
+        grad = torch.empty(B, T, 6, dtype=torch.float32, device=self.device) if want_grad else None
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cld_pair_loss(self._h, _ptr(traj), C.byref(cs), _ptr(gi), _ptr(value), _ptr(grad), B, self._stream()),
+                        "cld_pair_loss")
+        return (value, grad) if want_grad else value
+
     def goal_loss(self, traj, goal: Mapping, grad_in=None, want_grad=True):
         """Upstream's global waypoint losses on decoded plans [B,52,6] (descaled, sample-minor rows; `goal`: see _goal) ->
         (per-row values [B] as upstream files them under guide_losses, grad_in + scale * d value / d traj [B,52,6]); cld_goal_loss."""
@@ -745,7 +842,7 @@ class Engine:
         xn = torch.empty_like(mean) if z is not None else None
         gr = torch.empty_like(mean) if want_grad else None
         ws, wsn = self._workspace(B)
-        with torch.cuda.device(self.device), self._goal_term(guidance, B), self._social_term(guidance, B), self._map_source_term((guidance or {}).get("map_collision"), B):
+        with torch.cuda.device(self.device), self._goal_term(guidance, B), self._social_term(guidance, B), self._pair_term(guidance, B), self._map_source_term((guidance or {}).get("map_collision"), B):
             self._check(self.lib.cld_guidance_step(self._h, _ptr(mean), _ptr(cond), C.byref(cg), C.c_float(sigma), _ptr(z),
                                                    _ptr(mg), _ptr(xn), _ptr(gr), B, ws, wsn, self._stream()), "cld_guidance_step")
         out = (mg,) + ((xn,) if z is not None else ()) + ((gr,) if want_grad else ())
@@ -806,7 +903,7 @@ class Engine:
         x1 = torch.empty_like(x_T) if (want_x1 and 1 in range(0, self.n_timesteps, self.stride)) else None
         logp = torch.empty(B, dtype=torch.float32, device=self.device) if want_logp else None
         cfg = non_cond is not None and guidance_w != 0.0
-        with torch.cuda.device(self.device), self._goal_term(guidance, B), self._social_term(guidance, B), self._map_source_term((guidance or {}).get("map_collision"), B):
+        with torch.cuda.device(self.device), self._goal_term(guidance, B), self._social_term(guidance, B), self._pair_term(guidance, B), self._map_source_term((guidance or {}).get("map_collision"), B):
             if guidance is not None:
                 cg, keep = self._guidance(guidance, B)
                 non_cond = self._f32(non_cond, (B, COND)) if cfg else None
@@ -846,7 +943,7 @@ class Engine:
         gr = torch.empty_like(x_t) if guided and want_grad else None
         ws, wsn = self._workspace(2 * ((B + 15) // 16 * 16) if cfg else B)
         sigma = C.c_float()
-        with torch.cuda.device(self.device), self._goal_term(guidance, B), self._social_term(guidance, B), self._map_source_term((guidance or {}).get("map_collision"), B):
+        with torch.cuda.device(self.device), self._goal_term(guidance, B), self._social_term(guidance, B), self._pair_term(guidance, B), self._map_source_term((guidance or {}).get("map_collision"), B):
             self._check(self.lib.cld_sample_step(self._h, _ptr(x_t), _ptr(cond), _ptr(non_cond), C.c_float(guidance_w),
                                                  None if cg is None else C.byref(cg), int(t_idx), _ptr(z), _ptr(xn), _ptr(mean),
                                                  _ptr(mg), _ptr(gr), C.byref(sigma), B, ws, wsn, self._stream()), "cld_sample_step")

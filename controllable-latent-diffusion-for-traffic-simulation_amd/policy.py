@@ -21,6 +21,7 @@ from typing import Callable, Mapping, Optional
 import numpy as np
 import torch
 
+from . import _lib
 from ._lib import CldError
 from .dm_model import DmModel, repeat_guidance
 from .engine import raster_frames      # noqa: F401  (re-exported: the frames a map_source implies)
@@ -186,6 +187,15 @@ def refresh_collision_terms(g: Optional[Mapping], obs: Mapping, world=None):
     return out
 
 
+def refresh_pair_term(g: Optional[Mapping], obs: Mapping):
+    """The guidance dict `g` with the frames of its pair term taken from `obs` where it holds them (upstream's losses read
+    data_batch['world_from_agent'] and ['agent_from_world'] at every call, trajdata_utils.py:550-562): agent_from_world from `obs`,
+    or, when `obs` has only world_from_agent, none -- the library then takes the inverse rotation; nothing is modified in place."""
+    if g is None or g.get("pair") is None or obs.get("world_from_agent") is None:
+        return g
+    return dict(g, pair=dict(g["pair"], world_from_agent=obs["world_from_agent"], agent_from_world=obs.get("agent_from_world")))
+
+
 def refresh_social_term(g: Optional[Mapping], obs: Mapping):
     """The guidance dict `g` with the frames of its social-group term taken from `obs` where it holds them (upstream's loss reads
     data_batch['world_from_agent'] at every call, guidance_loss.py:1156); nothing is modified in place."""
@@ -226,7 +236,9 @@ class CldPolicy:
         only extent (and curr_speed) for it.  `social_group` configs (guidance_loss.py:1137-1207) are taken out first
         (social_groups_from_config; `data_batch` needs world_from_agent) and kept as guidance['social_group']; with
         follow_observation their frames follow every observation too.  `social_seed` seeds their draws (default 0); every
-        get_action moves their evaluation index on, so successive plans do not reuse draws."""
+        get_action moves their evaluation index on, so successive plans do not reuse draws.  The pair-relation configs
+        (`gptcollision`, `gptkeepdistance`, ...; pair_terms_from_config) are taken out before them and kept as guidance['pair'];
+        they read world_from_agent (and agent_from_world, when there) of `data_batch` and follow the observation likewise."""
         data_batch = opt.pop("data_batch", None)         # observation fields scene-coupled losses read (agent_collision: extent, world_from_agent, curr_speed)
         follow = bool(opt.pop("follow_observation", False))
         map_source = opt.pop("map_source", None)
@@ -234,8 +246,12 @@ class CldPolicy:
         if by not in ("any", "own"):
             raise ValueError(f"goal_reached_by={by!r} (any | own)")
         social_seed = int(opt.pop("social_seed", 0))
-        rest, social = social_groups_from_config(guidance_config_list, scene_index, data_batch)
-        base = guidance_from_config(rest, scene_index, data_batch=data_batch, map_source=map_source) if social is None or any(len(c) for c in rest) else {}
+        rest, pair = pair_terms_from_config(guidance_config_list, scene_index, data_batch)
+        rest, social = social_groups_from_config(rest, scene_index, data_batch)
+        peeled = social is not None or pair is not None
+        base = guidance_from_config(rest, scene_index, data_batch=data_batch, map_source=map_source) if not peeled or any(len(c) for c in rest) else {}
+        if pair is not None:
+            base["pair"] = pair
         if social is not None:
             base["social_group"] = dict(social, seed=social_seed)
         self._guidance = dict(base, **opt)
@@ -283,7 +299,9 @@ class CldPolicy:
         vals = (self.vae.engine.guidance_losses(traj.reshape(B * N, 52, 6), g).reshape(B, N, 4) if has_builtin
                 else torch.full((B, N, 4), float("nan"), device=traj.device))
         nan = torch.full((B, N), float("nan"), device=vals.device)
-        colv = mapv = goalv = socv = None
+        colv = mapv = goalv = socv = pairv = None
+        if g.get("pair") is not None:                # per (pair, sample) as upstream's classes return them (unweighted)
+            pairv = self.vae.engine.pair_loss(traj.reshape(B * N, 52, 6), dict(g["pair"], num_samp=N), want_grad=False)
         if g.get("social_group") is not None:        # unweighted per-row values (guidance_loss.py:1205); 0 outside the groups here, NaN below
             socv = self.vae.engine.social_group_loss(traj.reshape(B * N, 52, 6), dict(g["social_group"], num_samp=N), want_grad=False).reshape(B, N)
         if g.get("goal") is not None:                # unweighted per-row values, 0 for agents that have arrived (guidance_loss.py:1029,1133)
@@ -304,6 +322,10 @@ class CldPolicy:
                     mask = torch.zeros(B, dtype=torch.bool)
                     mask[idx] = True
                     mask = mask.to(vals.device)
+                    if c["name"] in PAIR_NAMES:      # the [N] value under EVERY agent of the scene (indiv_loss[agt_mask] = cur_loss, :2171)
+                        pv = pairv[g["pair"]["configs"].index((si, gi))]
+                        out["%s_scene_%03d_%02d" % (c["name"], si, gi)] = torch.where(mask[:, None], pv[None, :].expand(B, N), nan)
+                        continue
                     v = (colv if c["name"] == "agent_collision" else mapv if c["name"] == "map_collision" else
                          goalv if c["name"] in GOAL_KINDS else socv if c["name"] == "social_group" else vals[..., LOSS_COLUMN[c["name"]]])
                     out["%s_scene_%03d_%02d" % (c["name"], si, gi)] = torch.where(mask[:, None], v, nan)
@@ -331,6 +353,15 @@ class CldPolicy:
                     inside[torch.as_tensor(grp, dtype=torch.long)] = True
                 out["social_group_scene_000_%02d" % len(names[0])] = torch.where(inside.to(socv.device)[:, None], socv, nan)
                 names[0].append("social_group")
+            if pairv is not None:                     # one scene: every pair's value under every agent, keyed by the relation's config name
+                number = {v: k for k, v in _lib.PAIR_KINDS.items()}
+                config_name = {spec[0]: nm for nm, spec in PAIR_NAMES.items()}
+                kd = g["pair"]["kind"]
+                kd = [kd] * pairv.shape[0] if isinstance(kd, (str, int)) else list(kd)
+                for p in range(pairv.shape[0]):
+                    nm = config_name[kd[p] if isinstance(kd[p], str) else number[int(kd[p])]]
+                    out["%s_scene_000_%02d" % (nm, len(names[0]))] = pairv[p][None, :].expand(B, N).clone()
+                    names[0].append(nm)
         return out, names
 
     @torch.no_grad()
@@ -371,7 +402,7 @@ class CldPolicy:
             g = dict(g, guide_clean=True)
         from_cfg = g is self._guidance and self._guidance_cfg is not None
         if guidance is None and self._follow_observation:           # the collision terms of set_guidance follow this observation
-            g = refresh_social_term(refresh_collision_terms(g, obs_dict), obs_dict)
+            g = refresh_pair_term(refresh_social_term(refresh_collision_terms(g, obs_dict), obs_dict), obs_dict)
         if g is not None and g.get("social_group") is not None and guidance is None:
             # the plan's loop iterations take evaluation indices social_iter .. social_iter + loop_steps - 1, the values reported on the
             # final output (below) the one behind them
@@ -439,7 +470,7 @@ def closed_loop_rollout(policy: CldPolicy, cond_fn: Callable, centroid, yaw, cur
     of the previous plan taken into the new agent frame (the last one is the agent's position now), on the first step the current
     position repeated.  `step_index` = the sim step is the goal losses' global_t.
     With collision guidance that follows the observation (`set_guidance(..., follow_observation=True)`) the same holds for
-    `world_from_agent` (from the world pose; a social-group term reads it too), `curr_speed` (`curr_states[:, 2]`) and `world`
+    `world_from_agent` (from the world pose; a social-group or pair term reads it too), `curr_speed` (`curr_states[:, 2]`) and `world`
     [B,3], the pose itself, which a map_collision term in map mode is evaluated at; a raster-mode term needs `drivable_map` from `cond_fn` (SceneObserver gives it).
     Returns the world poses after each sim step [n_sim_steps, B, 3]."""
     import inspect
@@ -475,7 +506,7 @@ def closed_loop_rollout(policy: CldPolicy, cond_fn: Callable, centroid, yaw, cur
                         hw = world[:, None, :2].expand(-1, n_step_action, -1) if hist_world is None else hist_world
                         obs["agent_hist"] = transform_points(hw, torch.as_tensor(obs["agent_from_world"]).float().to(hw.device))
                 pg = policy._guidance or {}
-                if gk is None and policy._follow_observation and any(pg.get(k) is not None for k in ("agent_collision", "map_collision", "social_group")):
+                if gk is None and policy._follow_observation and any(pg.get(k) is not None for k in ("agent_collision", "map_collision", "social_group", "pair")):
                     obs = dict(obs)                   # the collision terms follow the observation: what cond_fn's lacks, from the loop's own state
                     if "world_from_agent" not in obs:
                         obs["world_from_agent"] = frames_from_pose(world)
@@ -500,6 +531,68 @@ def closed_loop_rollout(policy: CldPolicy, cond_fn: Callable, centroid, yaw, cur
                     scorer.add_plans(scored)
         poses.append(world)
     return torch.stack(poses)
+
+
+# upstream's pair-relation losses: config name -> (cld_pair_term kind, parameter names of (lo, hi, decay) and their defaults).  The first
+# two are upstream's GUIDANCE_FUNC_MAP names (CollisionLoss, KeepDistanceLoss); the other three are this project's names for classes
+# upstream reaches only through its language-model front end (StayAwayLoss / KeepDistanceLoss2, FrontCollisionLoss, CollideLeftSideLoss)
+PAIR_NAMES = {
+    "gptkeepdistance": ("keep_distance", 20, 1, (("min_distance", 5.0), ("max_distance", 15.0), None)),
+    "gptcollision": ("collision", 2, 3, (("collision_radius", 1.0), None, None)),
+    "gptstayaway": ("stay_away", 8, 1, (("min_dist", 5.0), ("max_dist", 15.0), ("decay_rate", 0.9))),
+    "gptfrontcollision": ("front_collision", 2, 3, (None, None, None)),
+    "gptcollideleftside": ("collide_left", 2, 3, (None, None, None)),
+}
+
+
+def pair_terms_from_config(guidance_config_list, scene_index, data_batch: Optional[Mapping] = None, num_samp: Optional[int] = None):
+    """Upstream's pair-relation configs taken out of a guidance configuration -> (the list without them, the `pair` entry of a
+    guidance dict -- Engine._pair -- or None when there is none).
+
+    Names and parameters (upstream's names and defaults, guidance_loss.py): `gptkeepdistance` (target_ind = 20, ref_ind = 1,
+    min_distance = 5, max_distance = 15), `gptcollision` (target_ind = 2, ref_ind = 3, collision_radius = 1), and this project's
+    names `gptstayaway` (StayAwayLoss: target_ind = 8, ref_ind = 1, min_dist = 5, max_dist = 15, decay_rate = 0.9; with other
+    parameters it is KeepDistanceLoss2), `gptfrontcollision` and `gptcollideleftside` (target_ind = 2, ref_ind = 3).  target_ind /
+    ref_ind index the agents of the config's scene and are mapped to batch indices here.  The term carries `weight` per pair --
+    Engine._pair folds weight / num_samp into the kernel's scale -- and, when `num_samp` is given, that `scale` itself; `configs`
+    [(scene, config index)] and `names` say where each pair came from.  agent_from_world is taken from `data_batch` when it is there.
+    ValueError: no world_from_agent in `data_batch`, an index outside the scene, target_ind == ref_ind, min > max.
+    NotImplementedError: an `agents` subset (upstream's classes index the masked plans with scene indices: a subset shifts them)."""
+    scene_index = torch.as_tensor(scene_index).reshape(-1).cpu()
+    _, local = torch.unique_consecutive(scene_index, return_inverse=True)
+    rest, term = [], None
+    for si, cfgs in enumerate(guidance_config_list):
+        keep = []
+        for gi, cfg in enumerate(cfgs):
+            if cfg["name"] not in PAIR_NAMES:
+                keep.append(cfg)
+                continue
+            if data_batch is None or data_batch.get("world_from_agent") is None:
+                raise ValueError(f"{cfg['name']} needs data_batch with world_from_agent")
+            if cfg.get("agents") is not None:
+                raise NotImplementedError(f"{cfg['name']} on an `agents` subset")
+            kind, d_target, d_ref, (p_lo, p_hi, p_decay) = PAIR_NAMES[cfg["name"]]
+            prm = cfg.get("params") or {}
+            members = torch.nonzero(local == si).reshape(-1)
+            ti, ri = int(prm.get("target_ind", d_target)), int(prm.get("ref_ind", d_ref))
+            for what, v in (("target_ind", ti), ("ref_ind", ri)):
+                if not 0 <= v < members.numel():
+                    raise ValueError(f"{cfg['name']}: {what} = {v} outside scene {si} of {members.numel()} agents")
+            if ti == ri:
+                raise ValueError(f"{cfg['name']}: target_ind == ref_ind = {ti}")
+            lo, hi, decay = (0.0 if q is None else float(prm.get(q[0], q[1])) for q in (p_lo, p_hi, p_decay))
+            if p_hi is not None and lo > hi:
+                raise ValueError(f"{cfg['name']}: min {lo} > max {hi}")
+            if term is None:
+                term = dict(target=[], ref=[], kind=[], lo=[], hi=[], decay=[], weight=[], configs=[], names=[],
+                            world_from_agent=data_batch["world_from_agent"], agent_from_world=data_batch.get("agent_from_world"))
+            for k, v in (("target", int(members[ti])), ("ref", int(members[ri])), ("kind", kind), ("lo", lo), ("hi", hi), ("decay", decay),
+                         ("weight", float(cfg["weight"])), ("configs", (si, gi)), ("names", cfg["name"])):
+                term[k].append(v)
+        rest.append(keep)
+    if term is not None and num_samp is not None:
+        term["scale"] = [w / int(num_samp) for w in term["weight"]]
+    return rest, term
 
 
 def social_groups_from_config(guidance_config_list, scene_index, data_batch: Optional[Mapping] = None):
@@ -567,7 +660,7 @@ def guidance_from_config(guidance_config_list, scene_index, horizon: int = 52, d
     weight / agents; at most one per agent, one dt and one min_progress_dist per call); at most
     one of each other loss per scene, one parameter set per call; the others (stop signs, lane keeping, ...) are not built, and
     `social_group` is refused HERE too: it is scene-coupled and random, and enters one level up (social_groups_from_config, which
-    CldPolicy.set_guidance calls first).  One speed / acceleration limit value per call."""
+    CldPolicy.set_guidance calls first); so do the pair-relation names (`gptcollision`, `gptkeepdistance`, ...: pair_terms_from_config).  One speed / acceleration limit value per call."""
     scene_index = torch.as_tensor(scene_index).reshape(-1).cpu()
     B = scene_index.numel()
     _, local = torch.unique_consecutive(scene_index, return_inverse=True)

@@ -411,6 +411,63 @@ int cld_social_group_loss(cld_handle h, const float* traj, const cld_social_grou
  * CLD_ERR_ARG, decided before anything is launched.  (A setter and not a pointer in cld_guidance: that struct's layout is frozen.) */
 int cld_set_social_term(cld_handle h, const cld_social_group* term);
 
+/* Upstream's pair-relation losses (src/tbsim/utils/guidance_loss.py): `gptkeepdistance` (KeepDistanceLoss, :1631-1688), `gptcollision`
+ * (CollisionLoss, :1691-1734), and the four classes of the same family upstream reaches only through its language-model front end:
+ * StayAwayLoss (:2014-2082) / KeepDistanceLoss2 (:1739-1791), FrontCollisionLoss (:1844-1896), CollideLeftSideLoss (:1899-1956).
+ * Pair p = (target[p], ref[p]), agent (batch) indices.  For every sample n and step t the plan positions of both agents go to the
+ * world frame (world_from_agent[a] (x, y)) and into the REF agent's static frame: q = M (p_target - p_ref), M the rotation of
+ * agent_from_world[ref] (NULL: the transpose of world_from_agent[ref]'s); the frame does not follow the plan's yaw.  d = |q|
+ * (CLD_PAIR_COLLISION: the world distance, as upstream takes it).  The step's term e_t:
+ *     CLD_PAIR_KEEP_DISTANCE     relu(lo - d) + relu(d - hi)
+ *     CLD_PAIR_COLLISION         relu(d - lo)                                  (lo = collision_radius; hi unused)
+ *     CLD_PAIR_STAY_AWAY         relu(d - hi) + relu(lo - d)                   (KeepDistanceLoss2's `where` form equals it for lo <= hi)
+ *     CLD_PAIR_FRONT_COLLISION   |Dx| + relu(-Dy),  D = -q = ref - target in the ref frame
+ *     CLD_PAIR_COLLIDE_LEFT      |Dx| + relu(Dy)
+ * value[p, n] = sum_t w_t e_t, w_t = 1 / 52, or with decay[p] > 0: decay^t / sum_t decay^t / 52 -- normalised AND divided by 52, as
+ * upstream does.  The term's total is sum over (p, n) of scale[p] * value[p, n] (scale = weight / num_samp reproduces upstream's
+ * weight * mean over the samples).  Both agents receive gradient, nothing is detached; only the x, y columns of the plans receive
+ * anything.  relu passes the gradient where its argument is >= 0 (torch.clip), the norm's gradient at d = 0 is 0, abs at 0 gives 0.
+ * An agent may sit in several pairs in either role, so the gradient is a gather: the caller lists, per involved agent, its
+ * incidences pair * 2 + role (role 0 = target, 1 = ref) in ascending order -- agent_id[k]'s are incidence[agent_start[k] ..
+ * agent_start[k + 1]); every agent_id once.  The order fixes the summation order.  Upstream runs these classes on a single-scene batch
+ * only (it indexes full-batch frames with masked plans, the defect recorded for MapCollisionLoss above); here the pairs of all scenes
+ * go into one launch.
+ * Contract on the device-side indices (as cld_social_group.max_members): a pair whose target or ref lies outside [0, A), or with
+ * target == ref, is not evaluated -- NaN value, no contribution; incidences that point outside the arrays or name a pair their agent
+ * is not part of are skipped.  NOT checked: that agent_id lists every agent once -- a duplicated agent_id stays inside the arrays, but
+ * two threads then add to one row and the bits of that row are no longer the same on every run.  Rows in no pair: gradient grad_in.  Deterministic: no atomics, the same bits on every run; plain fp32
+ * in both precisions.  Agents A = B / num_samp. */
+enum { CLD_PAIR_KEEP_DISTANCE = 0, CLD_PAIR_COLLISION = 1, CLD_PAIR_STAY_AWAY = 2, CLD_PAIR_FRONT_COLLISION = 3, CLD_PAIR_COLLIDE_LEFT = 4 };
+typedef struct cld_pair_term {
+    const int32_t* target;          /* DEVICE [num_pairs] agent (batch) index                                               */
+    const int32_t* ref;             /* DEVICE [num_pairs]                                                                   */
+    const int32_t* kind;            /* DEVICE [num_pairs] CLD_PAIR_*                                                        */
+    const float* lo;                /* DEVICE [num_pairs] min distance, or the collision radius                             */
+    const float* hi;                /* DEVICE [num_pairs] max distance                                                      */
+    const float* decay;             /* DEVICE [num_pairs] <= 0: a plain mean over the steps                                 */
+    const float* scale;             /* DEVICE [num_pairs] d total / d value of a (pair, sample)                             */
+    const float* world_from_agent;  /* DEVICE [A,3,3] row-major                                                             */
+    const float* agent_from_world;  /* DEVICE [A,3,3] or NULL                                                               */
+    const int32_t* agent_start;     /* DEVICE [num_involved + 1] offsets into incidence                                     */
+    const int32_t* agent_id;        /* DEVICE [num_involved] the agents that sit in a pair, each once                       */
+    const int32_t* incidence;       /* DEVICE [num_incidences] pair * 2 + role, ascending per agent                         */
+    int32_t num_pairs;
+    int32_t num_samp;
+    int32_t num_involved;
+    int32_t num_incidences;
+} cld_pair_term;
+
+/* The losses above on given plans: traj [B,52,6] descaled -> value [num_pairs, num_samp] (unweighted, as upstream's classes return
+ * them) and grad [B,52,6] = grad_in (when given; may be grad itself) + d total / d traj.  Either output may be NULL. */
+int cld_pair_loss(cld_handle h, const float* traj, const cld_pair_term* term, const float* grad_in, float* value, float* grad,
+                  int32_t B, void* stream);
+
+/* Keep a pair term on the handle (the struct is copied by value; NULL clears it).  While one is set, every guided call
+ * (cld_sample_guided, cld_sample_step, cld_guidance_step) adds its gradient after the social-group term's, on the same decoded
+ * iterate; it counts as a loss term of the `cld_guidance` it is used with.  A malformed term is CLD_ERR_ARG, decided before anything
+ * is launched.  (A setter and not a pointer in cld_guidance: that struct's layout is frozen.) */
+int cld_set_pair_term(cld_handle h, const cld_pair_term* term);
+
 /* cld_sample (non_cond == NULL) / cld_sample_cfg (non_cond != NULL) with the guidance step above inside the loop. */
 int cld_sample_guided(cld_handle h, const float* x_T, const float* noise, const float* cond, const float* non_cond,
                       float guidance_w, const cld_guidance* guidance, int32_t steps, float* x0, float* x1, float* logp,
