@@ -54,17 +54,22 @@ __device__ __forceinline__ void chain_grad(const DynParams& d, const GuideArgs& 
     const float* eg = a.ext_grad ? a.ext_grad + (size_t)b * GT * 6 : nullptr;
     const bool pos = s_tp != 0.f || eg != nullptr;
     // ---- forward ----
-    float v_raw = cs[2], x = cs[0], y = cs[1], yaw = cs[3];
-    vk[0] = fminf(fmaxf(v_raw, d.v_lo), d.v_hi);
-    th[0] = yaw;
+    // The four running sums (and the four of the backward sweep) are carried in double and read back rounded to float: 52 float
+    // additions at the magnitude of a position (70 m after 5 s at 14 m/s: 4e-6 m a step) or of a heading put the gradient of a
+    // position loss up to 1.8 times over the calibrated bar of tests/test_gpu_guide.py, whose float32 reference does not share them
+    // (torch.cumsum on the CPU carries a float32 sum in double), as in rollout_agent (misc_kernels.hip).
+    double v_raw = cs[2], x = cs[0], y = cs[1], yaw = cs[3];
+    vk[0] = fminf(fmaxf((float)v_raw, d.v_lo), d.v_hi);
+    th[0] = (float)yaw;
     gv[0] = 0.f;
     int tstar = 0;
     if (s_tp != 0.f) { tstar = a.target_time[b]; tstar = tstar > GT - 1 ? GT - 1 : tstar; }    // (target_* are null without the term)
     for (int t = 0; t < GT; ++t) {
         const float acc = act0[t * st] * d.std[4] + d.mean[4];
-        v_raw += fminf(fmaxf(acc, d.acc_lo), d.acc_hi) * d.dt;
-        const bool vok = v_raw >= d.v_lo && v_raw <= d.v_hi;
-        const float v = fminf(fmaxf(v_raw, d.v_lo), d.v_hi);
+        v_raw += (double)(fminf(fmaxf(acc, d.acc_lo), d.acc_hi) * d.dt);
+        const float vr = (float)v_raw;
+        const bool vok = vr >= d.v_lo && vr <= d.v_hi;
+        const float v = fminf(fmaxf(vr, d.v_lo), d.v_hi);
         vk[t + 1] = v;
         float g = 0.f;
         if (tgt) {
@@ -81,11 +86,11 @@ __device__ __forceinline__ void chain_grad(const DynParams& d, const GuideArgs& 
             const float wr = act1[t * st] * d.std[5] + d.mean[5];
             const float wc = fmaxf(fminf(wr, yb), -yb);
             const float vbar = 0.5f * (vk[t] + v);
-            x += vbar * cosf(yaw) * d.dt;
-            y += vbar * sinf(yaw) * d.dt;
-            yaw += wc * d.dt;
-            th[t + 1] = yaw;
-            gxk[t] = x; gyk[t] = y;             // positions for now
+            x += (double)(vbar * cosf(th[t]) * d.dt);
+            y += (double)(vbar * sinf(th[t]) * d.dt);
+            yaw += (double)(wc * d.dt);
+            th[t + 1] = (float)yaw;
+            gxk[t] = (float)x; gyk[t] = (float)y;             // positions for now
         }
     }
     if (pos && s_tp == 0.f) {
@@ -100,46 +105,48 @@ __device__ __forceinline__ void chain_grad(const DynParams& d, const GuideArgs& 
         } else {                                // hit it at SOME step >= m: L = mean_t w_t dist_t^2, w = softmin(dist)
             int m = -tstar - 1;
             m = m > GT - 1 ? GT - 1 : m;
-            float dmin = 3.4e38f;
+            // (in double: S - dist_t^2 below is a difference of squared distances, hundreds of m^2 for a waypoint 20 m away)
+            double dmin = 1e300;
             for (int t = m; t < GT; ++t) {
-                const float ex = gxk[t] - wx, ey = gyk[t] - wy;
-                dmin = fminf(dmin, sqrtf(ex * ex + ey * ey));
+                const double ex = (double)gxk[t] - wx, ey = (double)gyk[t] - wy;
+                dmin = fmin(dmin, sqrt(ex * ex + ey * ey));
             }
-            float z = 0.f, S = 0.f;
+            double z = 0.0, S = 0.0;
             for (int t = m; t < GT; ++t) {
-                const float ex = gxk[t] - wx, ey = gyk[t] - wy;
-                const float dd = sqrtf(ex * ex + ey * ey), e = expf(-(dd - dmin));
+                const double ex = (double)gxk[t] - wx, ey = (double)gyk[t] - wy;
+                const double dd = sqrt(ex * ex + ey * ey), e = exp(-(dd - dmin));
                 z += e; S += e * dd * dd;
             }
             S /= z;
-            const float inv = s_tp / (float)(GT - m);
+            const double inv = (double)s_tp / (double)(GT - m);
             for (int t = 0; t < GT; ++t) {
                 if (t < m) { gxk[t] = 0.f; gyk[t] = 0.f; continue; }
-                const float ex = gxk[t] - wx, ey = gyk[t] - wy;
-                const float dd = sqrtf(ex * ex + ey * ey), wgt = expf(-(dd - dmin)) / z;
+                const double ex = (double)gxk[t] - wx, ey = (double)gyk[t] - wy;
+                const double dd = sqrt(ex * ex + ey * ey), wgt = exp(-(dd - dmin)) / z;
                 // d/dp_t [ sum_s w_s dist_s^2 ] = w_t (2 e_t + (S - dist_t^2) e_t / dist_t)
-                const float k = inv * wgt * (2.f + (dd > 0.f ? (S - dd * dd) / dd : 0.f));
-                gxk[t] = k * ex; gyk[t] = k * ey;
+                const double k = inv * wgt * (2.0 + (dd > 0.0 ? (S - dd * dd) / dd : 0.0));
+                gxk[t] = (float)(k * ex); gyk[t] = (float)(k * ey);
             }
         }
     }
     // ---- backward ----
-    float gx = 0.f, gy = 0.f;                   // dL/dx_{k+1}, dL/dy_{k+1} summed over k >= current step (suffix sums)
-    float g_th_suffix = 0.f;                    // sum_{m > k} dL/dth_m
-    float run_v = 0.f;                          // sum_{k > j} dL/dv_raw_k
+    double gxs = 0.0, gys = 0.0;                // dL/dx_{k+1}, dL/dy_{k+1} summed over k >= current step (suffix sums)
+    double g_th_suffix = 0.0;                   // sum_{m > k} dL/dth_m
+    double run_v = 0.0;                         // sum_{k > j} dL/dv_raw_k
     float d_vbar_next = 0.f;                    // dL/dvbar_{k+1}
     for (int k = GT - 1; k >= 0; --k) {
         float d_w = 0.f, d_vk_from_yb = 0.f, d_vbar = 0.f;
         if (pos) {
-            gx += gxk[k]; gy += gyk[k];
-            if (eg) { gx += eg[k * 6 + 0]; gy += eg[k * 6 + 1]; g_th_suffix += eg[k * 6 + 3]; }     // direct terms on x_{k+1}, y_{k+1}, th_{k+1}
+            gxs += gxk[k]; gys += gyk[k];
+            if (eg) { gxs += eg[k * 6 + 0]; gys += eg[k * 6 + 1]; g_th_suffix += eg[k * 6 + 3]; }     // direct terms on x_{k+1}, y_{k+1}, th_{k+1}
+            const float gx = (float)gxs, gy = (float)gys;
             float sn, cn;
             sincosf(th[k], &sn, &cn);
             const float vbar = 0.5f * (vk[k] + vk[k + 1]);
             d_vbar = d.dt * (gx * cn + gy * sn);
             const float d_thk = d.dt * vbar * (-gx * sn + gy * cn);              // dL/dth_k through the positions
             // th_m for m > k depends on wc_k
-            const float d_wc = d.dt * g_th_suffix;
+            const float d_wc = d.dt * (float)g_th_suffix;
             const float av = fabsf(vk[k]);
             const float ya = d.max_steer * av, ybb = d.max_yawvel / fmaxf(av, 0.1f);
             const float yb = fmaxf(fminf(ya, ybb), 0.1f);
@@ -158,7 +165,7 @@ __device__ __forceinline__ void chain_grad(const DynParams& d, const GuideArgs& 
         // (the yaw-bound path of v_{k+1}, as v_prev of step k+1, was added into gv[k+1] by the iteration above)
         run_v += d_vk1;
         const float acc = act0[k * st] * d.std[4] + d.mean[4];
-        float g = (acc >= d.acc_lo && acc <= d.acc_hi) ? run_v * d.dt : 0.f;
+        float g = (acc >= d.acc_lo && acc <= d.acc_hi) ? (float)run_v * d.dt : 0.f;
         if (s_al != 0.f && fabsf(acc) - a.acc_limit > 0.f) g += s_al * ((acc > 0.f) ? 1.f : -1.f);
         if (eg) g += eg[k * 6 + 4];                                                // ... and the unclipped descaled acceleration
         dact0[k] = g * d.std[4];
@@ -209,12 +216,13 @@ __device__ __forceinline__ void chain_grad_group(const DynParams& d, const Guide
         const int ag = tid;
         const float* cs = a.curr_states + (size_t)agent(ag) * 4;
         float* vk = row(ag, VK); float* mk = row(ag, MASK); const float* ac = row(ag, ACCC);
-        float v_raw = cs[2];
-        vk[0] = fminf(fmaxf(v_raw, d.v_lo), d.v_hi);
+        double v_raw = cs[2];                   // (the running sums in double, read back as float: see chain_grad)
+        vk[0] = fminf(fmaxf((float)v_raw, d.v_lo), d.v_hi);
         for (int t = 0; t < GT; ++t) {
-            v_raw += ac[t] * d.dt;
-            mk[t + 1] = (v_raw >= d.v_lo && v_raw <= d.v_hi) ? 1.f : 0.f;
-            vk[t + 1] = fminf(fmaxf(v_raw, d.v_lo), d.v_hi);
+            v_raw += (double)(ac[t] * d.dt);
+            const float vr = (float)v_raw;
+            mk[t + 1] = (vr >= d.v_lo && vr <= d.v_hi) ? 1.f : 0.f;
+            vk[t + 1] = fminf(fmaxf(vr, d.v_lo), d.v_hi);
         }
     }
     __syncthreads();
@@ -247,9 +255,9 @@ __device__ __forceinline__ void chain_grad_group(const DynParams& d, const Guide
         const Consts c = consts(ag);
         if (c.pos) {
             float* th = row(ag, TH); const float* wc = row(ag, WC);
-            float yaw = c.cs[3];
-            th[0] = yaw;
-            for (int t = 0; t < GT; ++t) { yaw += wc[t] * d.dt; th[t + 1] = yaw; }
+            double yaw = c.cs[3];
+            th[0] = (float)yaw;
+            for (int t = 0; t < GT; ++t) { yaw += (double)(wc[t] * d.dt); th[t + 1] = (float)yaw; }
         }
     }
     __syncthreads();
@@ -273,8 +281,8 @@ __device__ __forceinline__ void chain_grad_group(const DynParams& d, const Guide
         float* gxk = row(ag, GXK); float* gyk = row(ag, GYK);
         if (c.pos) {
             const float* cx = row(ag, CX); const float* cy = row(ag, CY);
-            float x = c.cs[0], y = c.cs[1];
-            for (int t = 0; t < GT; ++t) { x += cx[t] * d.dt; y += cy[t] * d.dt; gxk[t] = x; gyk[t] = y; }
+            double x = c.cs[0], y = c.cs[1];
+            for (int t = 0; t < GT; ++t) { x += (double)(cx[t] * d.dt); y += (double)(cy[t] * d.dt); gxk[t] = (float)x; gyk[t] = (float)y; }
             if (c.s_tp == 0.f) {
                 for (int t = 0; t < GT; ++t) { gxk[t] = 0.f; gyk[t] = 0.f; }
             } else {      // positions -> direct position gradients (as in chain_grad)
@@ -288,33 +296,34 @@ __device__ __forceinline__ void chain_grad_group(const DynParams& d, const Guide
                 } else {
                     int m = -tstar - 1;
                     m = m > GT - 1 ? GT - 1 : m;
-                    float dmin = 3.4e38f;
+                    // (in double: S - dist_t^2 below is a difference of squared distances, hundreds of m^2 for a waypoint 20 m away)
+                    double dmin = 1e300;
                     for (int t = m; t < GT; ++t) {
-                        const float ex = gxk[t] - wx, ey = gyk[t] - wy;
-                        dmin = fminf(dmin, sqrtf(ex * ex + ey * ey));
+                        const double ex = (double)gxk[t] - wx, ey = (double)gyk[t] - wy;
+                        dmin = fmin(dmin, sqrt(ex * ex + ey * ey));
                     }
-                    float z = 0.f, S = 0.f;
+                    double z = 0.0, S = 0.0;
                     for (int t = m; t < GT; ++t) {
-                        const float ex = gxk[t] - wx, ey = gyk[t] - wy;
-                        const float dd = sqrtf(ex * ex + ey * ey), e = expf(-(dd - dmin));
+                        const double ex = (double)gxk[t] - wx, ey = (double)gyk[t] - wy;
+                        const double dd = sqrt(ex * ex + ey * ey), e = exp(-(dd - dmin));
                         z += e; S += e * dd * dd;
                     }
                     S /= z;
-                    const float inv = c.s_tp / (float)(GT - m);
+                    const double inv = (double)c.s_tp / (double)(GT - m);
                     for (int t = 0; t < GT; ++t) {
                         if (t < m) { gxk[t] = 0.f; gyk[t] = 0.f; continue; }
-                        const float ex = gxk[t] - wx, ey = gyk[t] - wy;
-                        const float dd = sqrtf(ex * ex + ey * ey), wgt = expf(-(dd - dmin)) / z;
-                        const float k = inv * wgt * (2.f + (dd > 0.f ? (S - dd * dd) / dd : 0.f));
-                        gxk[t] = k * ex; gyk[t] = k * ey;
+                        const double ex = (double)gxk[t] - wx, ey = (double)gyk[t] - wy;
+                        const double dd = sqrt(ex * ex + ey * ey), wgt = exp(-(dd - dmin)) / z;
+                        const double k = inv * wgt * (2.0 + (dd > 0.0 ? (S - dd * dd) / dd : 0.0));
+                        gxk[t] = (float)(k * ex); gyk[t] = (float)(k * ey);
                     }
                 }
             }
-            float gx = 0.f, gy = 0.f;           // dL/dx_{k+1}, dL/dy_{k+1} summed over the steps >= k
+            double gx = 0.0, gy = 0.0;          // dL/dx_{k+1}, dL/dy_{k+1} summed over the steps >= k
             for (int k = GT - 1; k >= 0; --k) {
                 gx += gxk[k]; gy += gyk[k];
                 if (c.eg) { gx += c.eg[k * 6 + 0]; gy += c.eg[k * 6 + 1]; }
-                gxk[k] = gx; gyk[k] = gy;
+                gxk[k] = (float)gx; gyk[k] = (float)gy;
             }
         }
     }
@@ -342,10 +351,10 @@ __device__ __forceinline__ void chain_grad_group(const DynParams& d, const Guide
         const Consts c = consts(ag);
         if (c.pos) {
             const float* dth = row(ag, DTH); float* ths = row(ag, THS);
-            float g = 0.f;                      // sum_{m > k} dL/dth_m (+ the direct terms on th_{m}, m > k)
+            double g = 0.0;                     // sum_{m > k} dL/dth_m (+ the direct terms on th_{m}, m > k)
             for (int k = GT - 1; k >= 0; --k) {
                 if (c.eg) g += c.eg[k * 6 + 3];
-                ths[k] = g;
+                ths[k] = (float)g;
                 g += dth[k];
             }
         }
@@ -387,8 +396,8 @@ __device__ __forceinline__ void chain_grad_group(const DynParams& d, const Guide
     if (tid < AGN) {
         const int ag = tid;
         const float* dv = row(ag, DVK1); float* rn = row(ag, RUN);
-        float run = 0.f;
-        for (int k = GT - 1; k >= 0; --k) { run += dv[k]; rn[k] = run; }
+        double run = 0.0;
+        for (int k = GT - 1; k >= 0; --k) { run += dv[k]; rn[k] = (float)run; }
     }
     __syncthreads();
     // ---- P8: dL/d acceleration action ----

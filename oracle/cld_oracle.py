@@ -666,7 +666,7 @@ def context_encode(w: Dict[str, Tensor], image: Tensor, curr_states: Tensor, tap
 def guidance_step(wdec, mean: Tensor, cond: Tensor, cs: Tensor, target_speed: Optional[Tensor], loss_scale: Optional[Tensor],
                   lr: float, perturb_th: Optional[float], optimizer: str = "adam", speed_limit=None, acc_limit=None, target_pos=None,
                   collision: Optional[dict] = None, grad_steps: int = 1, num_samp: int = 1, map_collision: Optional[dict] = None,
-                  trace: Optional[list] = None):
+                  trace: Optional[list] = None, decoder=None, ext_grad: Optional[Tensor] = None):
     """One PerturbationGuidance.perturb call (guidance_loss.py:2221-2282) with decoder = `decode` and
     TargetSpeedLoss (:219-254): L = sum_b loss_scale[b] * sum_t |v_t - target| (+ optional SpeedLimitLoss / AccLimitLoss
     terms, each a (limit, per-agent scale) pair; + `collision`: the agent_collision configs, see scene_collision_total).
@@ -676,12 +676,15 @@ def guidance_step(wdec, mean: Tensor, cond: Tensor, cs: Tensor, target_speed: Op
     reference's actual behaviour: its clip (:2275-2278) acts on x_guidance - x_initial, two names of one tensor
     (:2239), so it never changes anything (the golden vectors confirm); a number clips the accumulated step to +- that
     around the initial mean, as the code intends.  Returns (guided mean, gradient of the first step); `trace` (a list) receives every
-    step's gradient."""
+    step's gradient.  decoder: a stand-in for `decode` with descaled output, (wdec, x, cond, cs) -> [B,52,6] (the tests restate the
+    decoder's gates in a kernel's arithmetic with it).  ext_grad [B,52,6]: the term sum(traj * ext_grad), a loss computed elsewhere on
+    the decoded trajectory and known by its gradient (Engine.decode_vjp).  NaN entries of target_speed count as no target
+    (guidance_loss.py:247, nan_to_num on the deviation)."""
     def total(x):
-        traj = decode(wdec, x, cond, cs, True)
+        traj = decode(wdec, x, cond, cs, True) if decoder is None else decoder(wdec, x, cond, cs)
         loss = traj.sum() * 0.0
         if target_speed is not None:
-            dev = (traj[..., 2] - target_speed).abs()
+            dev = torch.nan_to_num((traj[..., 2] - target_speed).abs(), nan=0.0)
             sc = loss_scale if loss_scale is not None else torch.full((mean.shape[0],), 1.0 / mean.shape[1], dtype=mean.dtype)
             loss = loss + (dev.sum(dim=1) * sc).sum()
         if speed_limit is not None:        # (limit, scale [B]): SpeedLimitLoss, guidance_loss.py:1509-1538
@@ -702,6 +705,8 @@ def guidance_step(wdec, mean: Tensor, cond: Tensor, cs: Tensor, target_speed: Op
             loss = loss + scene_collision_total(traj, collision, num_samp)
         if map_collision is not None:
             loss = loss + scene_map_collision_total(traj, map_collision, num_samp)
+        if ext_grad is not None:
+            loss = loss + (traj * ext_grad).sum()
         return loss
 
     x = mean.clone()
