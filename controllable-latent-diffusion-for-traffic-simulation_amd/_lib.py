@@ -124,6 +124,17 @@ class CldPairTerm(C.Structure):
 PAIR_KINDS = {"keep_distance": 0, "collision": 1, "stay_away": 2, "front_collision": 3, "collide_left": 4}
 
 
+class CldLaneTerm(C.Structure):
+    """include/cld_lane.h `cld_lane_term` (upstream's lane-projection losses over the entries of a batch, device pointers)."""
+    _fields_ = [("lines", C.c_void_p), ("agent", C.c_void_p), ("line", C.c_void_p), ("kind", C.c_void_p), ("decay", C.c_void_p),
+                ("scale", C.c_void_p), ("num_entries", C.c_int32), ("num_lines", C.c_int32), ("max_pts", C.c_int32), ("num_samp", C.c_int32)]
+
+
+# include/cld_lane.h CLD_LANE_*: the loss a lane entry evaluates
+LANE_KINDS = {"following": 0, "change_left": 1, "follow_decayed": 2}
+LANE_MAX_PTS = 1024                    # include/cld_lane.h CLD_LANE_MAX_PTS
+
+
 class CldRaster(C.Structure):
     """include/cld.h `cld_raster` (the scene an observation raster is built from, device pointers)."""
     _fields_ = [("hist_world", C.c_void_p), ("hist_avail", C.c_void_p), ("scene_start", C.c_void_p), ("maps", C.c_void_p),
@@ -277,6 +288,13 @@ SIGNATURES = {
     "cld_version": (C.c_char_p, []),
 }
 
+# name -> (restype, argtypes); every symbol include/cld_lane.h declares (a table of its own: the one above is pinned to cld.h)
+LANE_SIGNATURES = {
+    "cld_lane_prepare": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P]),
+    "cld_lane_loss": (C.c_int, [_P, _P, C.POINTER(CldLaneTerm), _P, _P, _P, _P, C.c_int32, _P]),
+    "cld_set_lane_term": (C.c_int, [_P, C.POINTER(CldLaneTerm)]),
+}
+
 _lib = None
 
 
@@ -294,9 +312,10 @@ def load():
     # library first would pull /opt/rocm's runtime in beside torch's and break device init.
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)          # AttributeError if the library does not export it
-        fn.restype, fn.argtypes = res, args
+    for table in (SIGNATURES, LANE_SIGNATURES):
+        for name, (res, args) in table.items():
+            fn = getattr(lib, name)      # AttributeError if the library does not export it
+            fn.restype, fn.argtypes = res, args
     _lib = lib
     return lib
 

@@ -11,7 +11,9 @@
 #include <vector>
 
 #include "../../include/cld.h"
+#include "../../include/cld_lane.h"
 #include "cld_kernels.h"
+#include "lane_kernels.h"
 #include "train.h"
 
 using namespace cld;
@@ -58,6 +60,8 @@ struct cld_handle_s {
     bool has_social = false;
     cld_pair_term pair{};                            // cld_set_pair_term: the pair-relation term every guided call adds while has_pair
     bool has_pair = false;
+    cld_lane_term lane{};                            // cld_set_lane_term: the lane term every guided call adds while has_lane
+    bool has_lane = false;
     cld_map_source map_source{};                     // cld_set_map_source: what a cld_map_collision without a drivable_map reads while has_map_source
     bool has_map_source = false;
     std::vector<void*> dev_allocs;
@@ -1564,9 +1568,28 @@ static PairArgs pair_args(const cld_pair_term* t, const float* traj, float* valu
     return a;
 }
 
+static int check_lane(cld_handle h, const char* fn, const cld_lane_term* t, int B) {
+    if (!t->lines || !t->agent || !t->line || !t->kind || !t->decay || !t->scale)
+        return fail(h, CLD_ERR_ARG, std::string(fn) + ": lane term: null pointer");
+    if (t->num_entries < 1 || t->num_lines < 1 || t->num_samp < 1 || B % t->num_samp)
+        return fail(h, CLD_ERR_ARG, std::string(fn) + ": lane term: B must be agents x num_samp, num_entries >= 1, num_lines >= 1");
+    if (t->max_pts < 2 || t->max_pts > CLD_LANE_MAX_PTS)
+        return fail(h, CLD_ERR_ARG, std::string(fn) + ": lane term: max_pts must be 2 .. " + std::to_string(CLD_LANE_MAX_PTS));
+    if ((int64_t)t->num_entries * t->num_samp > INT32_MAX)
+        return fail(h, CLD_ERR_ARG, std::string(fn) + ": lane term: too many entries for one launch");
+    return CLD_OK;
+}
+static LaneArgs lane_args(const cld_lane_term* t, const float* traj, float* value, float* proj, float* grad, int B) {
+    LaneArgs a{};
+    a.traj = traj; a.lines = t->lines; a.agent = t->agent; a.line = t->line; a.kind = t->kind; a.decay = t->decay; a.scale = t->scale;
+    a.value = value; a.proj = proj; a.grad = grad; a.rows = B; a.num_entries = t->num_entries; a.num_lines = t->num_lines; a.max_pts = t->max_pts;
+    a.num_samp = t->num_samp;
+    return a;
+}
+
 static int check_guidance(cld_handle h, const char* fn, const cld_guidance* gd, int B, int iters = 1) {
     if (!h->has_decoder) return fail(h, CLD_ERR_STATE, std::string(fn) + ": guidance needs the decoder weights");
-    if (!gd->curr_states || (!gd->target_speed && !gd->speed_limit_scale && !gd->acc_limit_scale && !gd->target_pos_scale && !gd->ext_grad && !gd->collision && !gd->map_collision && !h->has_goal && !h->has_social && !h->has_pair))
+    if (!gd->curr_states || (!gd->target_speed && !gd->speed_limit_scale && !gd->acc_limit_scale && !gd->target_pos_scale && !gd->ext_grad && !gd->collision && !gd->map_collision && !h->has_goal && !h->has_social && !h->has_pair && !h->has_lane))
         return fail(h, CLD_ERR_ARG, std::string(fn) + ": guidance needs curr_states and at least one loss term");
     if (gd->collision) {
         const int rcc = check_collision(h, fn, gd->collision, B);
@@ -1588,6 +1611,10 @@ static int check_guidance(cld_handle h, const char* fn, const cld_guidance* gd, 
     }
     if (h->has_pair) {
         const int rcc = check_pair(h, fn, &h->pair, B);
+        if (rcc) return rcc;
+    }
+    if (h->has_lane) {
+        const int rcc = check_lane(h, fn, &h->lane, B);
         if (rcc) return rcc;
     }
     if (gd->optimizer != CLD_GUIDE_ADAM && gd->optimizer != CLD_GUIDE_SGD) return fail(h, CLD_ERR_ARG, std::string(fn) + ": unknown optimizer");
@@ -1622,7 +1649,7 @@ static int run_guidance(cld_handle h, const Ws& w, const cld_guidance* gd, int B
         const bool last = k == steps;
         g.opt_step = k;
         g.mean = k == 1 ? mean0 : w.gcur;
-        if (gd->collision || gd->map_collision || h->has_goal || h->has_social || h->has_pair) {    // the scene / map / goal / social / pair terms are functions of the decoded plans of the current iterate
+        if (gd->collision || gd->map_collision || h->has_goal || h->has_social || h->has_pair || h->has_lane) {    // the scene / map / goal / social / pair / lane terms are functions of the decoded plans of the current iterate
             if (B >= 256 && guide_forward_available(B, h->force_kernel[CLD_KERNEL_GUIDE]) && h->force_kernel[CLD_KERNEL_DECODE] == FORM_AUTO) {
                 // (from the batch size at which cld_decode itself would take its 16-agent MFMA form, ~0.3 ms; below that the
                 //  one-agent-per-workgroup decoder is the shorter chain: 64 agents 579 vs 616 us per collision-guided step)
@@ -1665,6 +1692,11 @@ static int run_guidance(cld_handle h, const Ws& w, const cld_guidance* gd, int B
         if (h->has_pair) {                           // after the social term's, on the same decoded iterate
             const float* gin = (gd->collision || gd->map_collision || h->has_goal || h->has_social) ? w.col_grad : gd->ext_grad;
             HIPCK(h, launch_pair(pair_args(&h->pair, w.col_traj, nullptr, w.col_grad, B), gin, s));
+            g.ext_grad = w.col_grad;
+        }
+        if (h->has_lane) {                           // after the pair term's, on the same decoded iterate
+            const float* gin = (gd->collision || gd->map_collision || h->has_goal || h->has_social || h->has_pair) ? w.col_grad : gd->ext_grad;
+            HIPCK(h, launch_lane(lane_args(&h->lane, w.col_traj, nullptr, nullptr, w.col_grad, B), gin, s));
             g.ext_grad = w.col_grad;
         }
         g.z = last ? z : nullptr;
@@ -2132,6 +2164,37 @@ int cld_set_pair_term(cld_handle h, const cld_pair_term* term) {
     if (!h) return CLD_ERR_ARG;
     h->has_pair = term != nullptr;
     h->pair = term ? *term : cld_pair_term{};
+    return CLD_OK;
+}
+
+int cld_lane_prepare(cld_handle h, const double* world_lines, const int32_t* line_frame, const float* agent_from_world, float* lines,
+                     int32_t num_lines, int32_t max_pts, int32_t num_frames, void* stream) {
+    if (!h) return CLD_ERR_ARG;
+    if (!world_lines || !line_frame || !agent_from_world || !lines || num_lines < 1 || num_frames < 1)
+        return fail(h, CLD_ERR_ARG, "cld_lane_prepare: bad argument");
+    if (max_pts < 1 || max_pts > CLD_LANE_MAX_PTS)
+        return fail(h, CLD_ERR_ARG, "cld_lane_prepare: max_pts must be 1 .. " + std::to_string(CLD_LANE_MAX_PTS));
+    LanePrepareArgs a{};
+    a.world_lines = world_lines; a.line_frame = line_frame; a.agent_from_world = agent_from_world; a.lines = lines;
+    a.num_lines = num_lines; a.max_pts = max_pts; a.num_frames = num_frames;
+    HIPCK(h, launch_lane_prepare(a, static_cast<hipStream_t>(stream)));
+    return CLD_OK;
+}
+
+int cld_lane_loss(cld_handle h, const float* traj, const cld_lane_term* term, const float* grad_in, float* value, float* proj,
+                  float* grad, int32_t B, void* stream) {
+    if (!h) return CLD_ERR_ARG;
+    if (!traj || !term || B < 1 || (!value && !proj && !grad)) return fail(h, CLD_ERR_ARG, "cld_lane_loss: bad argument");
+    int rc = check_lane(h, "cld_lane_loss", term, B);
+    if (rc) return rc;
+    HIPCK(h, launch_lane(lane_args(term, traj, value, proj, grad, B), grad_in, static_cast<hipStream_t>(stream)));
+    return CLD_OK;
+}
+
+int cld_set_lane_term(cld_handle h, const cld_lane_term* term) {
+    if (!h) return CLD_ERR_ARG;
+    h->has_lane = term != nullptr;
+    h->lane = term ? *term : cld_lane_term{};
     return CLD_OK;
 }
 

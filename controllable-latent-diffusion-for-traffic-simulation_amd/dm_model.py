@@ -58,7 +58,7 @@ def repeat_guidance(guidance: Mapping, num_samp: int, curr_states=None) -> dict:
     for k in ("speed_limit", "acc_limit", "target_pos"):
         if g.get(k) is not None:
             g[k] = tuple(rep(v) for v in g[k])
-    for k in ("agent_collision", "map_collision", "goal", "social_group", "pair"):  # per-AGENT tensors stay as they are: sample n of every agent lives in scene copy n
+    for k in ("agent_collision", "map_collision", "goal", "social_group", "pair", "lane"):  # per-AGENT tensors stay as they are: sample n of every agent lives in scene copy n
         if g.get(k) is not None:
             g[k] = dict(g[k], num_samp=num_samp)
     return g

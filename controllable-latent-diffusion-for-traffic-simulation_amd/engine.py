@@ -349,7 +349,8 @@ class Engine:
         acc_limit (limit, scale) | None, target_pos (pos [B,2], time index [B], scale) | None, lr | None, perturb_th | None | "sigma", optimizer "adam" | "sgd",
         grad_steps = 1, guide_clean = False, agent_collision: dict | None (see _collision), map_collision: dict | None (see _map_collision),
         goal: dict | None (see _goal; not part of the struct: sample / sample_step / guidance_step keep it on the handle for the call),
-        social_group: dict | None (see _social; kept on the handle for the call likewise), pair: dict | None (see _pair; likewise))
+        social_group: dict | None (see _social; kept on the handle for the call likewise), pair: dict | None (see _pair; likewise),
+        lane: dict | None (see _lane; likewise))
         -> (CldGuidance, tensors kept alive).  A `scale` is a per-agent tensor [B] (weight / (agents of the scene * 52),
         as DiffuserGuidance averages) or a scalar weight (divided by 52 here).  lr None = sigma_t; perturb_th None = no clip (what
         the reference's perturb() does), "sigma" = clip to sigma_t, a number = clip to it (include/cld.h)."""
@@ -770,6 +771,126 @@ class Engine:
                         "cld_pair_loss")
         return (value, grad) if want_grad else value
 
+    def lane_prepare(self, world_lines, line_frame, agent_from_world):
+        """World-frame polylines [L,S,3] (x, y, heading; float64, NaN-padded), line_frame [L] (the row of agent_from_world [A,3,3] a
+        line is taken into) -> agent-frame float32 polylines [L,S,3] sorted by (x, original index), NaN rows last: what a lane term
+        reads (cld_lane_prepare; upstream's get_lane_projection from transform_xyh_np to the sort, trajdata_utils.py:573-656).
+        S <= _lib.LANE_MAX_PTS."""
+        wl = world_lines if isinstance(world_lines, torch.Tensor) else torch.as_tensor(np.asarray(world_lines))
+        wl = wl.to(device=self.device, dtype=torch.float64).contiguous()
+        if wl.dim() != 3 or wl.shape[2] != 3 or wl.shape[0] < 1:
+            raise CldError(f"lane_prepare: world_lines must be [L,S,3], got {tuple(wl.shape)}")
+        L, S = int(wl.shape[0]), int(wl.shape[1])
+        afw = self._f32(agent_from_world)
+        if afw.dim() != 3 or tuple(afw.shape[1:]) != (3, 3):
+            raise CldError(f"lane_prepare: agent_from_world must be [A,3,3], got {tuple(afw.shape)}")
+        fr = torch.as_tensor(line_frame).reshape(-1).to(device=self.device, dtype=torch.int32).contiguous()
+        if fr.numel() != L:
+            raise CldError(f"lane_prepare: {fr.numel()} frame indices for {L} lines")
+        out = torch.empty(L, S, 3, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cld_lane_prepare(self._h, _ptr(wl), _ptr(fr), _ptr(afw), _ptr(out), L, S, int(afw.shape[0]), self._stream()),
+                        "cld_lane_prepare")
+        return out
+
+    def _lane(self, c: Mapping, B: int):
+        """dict(agent [E]: agent (batch) indices, an agent's entries contiguous; line [E]: indices into the polylines; kind [E]: a name
+        or number of _lib.LANE_KINDS (scalar or per entry); decay = 0.9 (follow_decayed), scalar or per entry; scale [E] (d total /
+        d value of an (entry, sample)) or weight [E] (scale = weight / num_samp); the polylines either prepared, lines [L,S,3]
+        (lane_prepare), or world_lines [L,S,3] float64 + agent_from_world [A,3,3] + line_frame [L] (default: the agent of the first
+        entry that reads the line), prepared here; num_samp = 1; validate = True: an entry outside the batch or the polylines, or an
+        agent whose entries are not contiguous, is a CldError; False: the entry reaches the kernel, which gives it a NaN value and
+        no gradient) -> (CldLaneTerm, tensors kept alive): upstream's lane-projection losses (guidance_loss.py:1574-1628,
+        1795-1841, 1958-2011) over all entries of the batch.  B = A * num_samp."""
+        N = int(c.get("num_samp", 1))
+        if N < 1 or B % N:
+            raise CldError(f"lane: {B} rows are not a multiple of num_samp = {N}")
+        A = B // N
+        missing = [k for k in ("agent", "line", "kind") if c.get(k) is None]
+        if missing or (c.get("scale") is None and c.get("weight") is None) or (c.get("lines") is None and c.get("world_lines") is None):
+            raise CldError(f"lane: missing {missing or ['scale | weight, lines | world_lines']}")
+        ag = [int(v) for v in torch.as_tensor(c["agent"]).reshape(-1).tolist()]
+        ln = [int(v) for v in torch.as_tensor(c["line"]).reshape(-1).tolist()]
+        E = len(ag)
+        if E < 1 or len(ln) != E:
+            raise CldError(f"lane: agent and line must name the same number (>= 1) of entries, got {E} / {len(ln)}")
+        if c.get("lines") is not None:
+            lines = self._f32(c["lines"])
+        else:
+            if c.get("agent_from_world") is None:
+                raise CldError("lane: world_lines need agent_from_world")
+            fr = c.get("line_frame")
+            if fr is None:
+                first = {}
+                for a, l in zip(ag, ln):
+                    first.setdefault(l, a)
+                fr = [first.get(l, -1) for l in range(int(torch.as_tensor(c["world_lines"]).shape[0]))]
+            lines = self.lane_prepare(c["world_lines"], fr, c["agent_from_world"])
+        if lines.dim() != 3 or lines.shape[2] != 3 or not 2 <= lines.shape[1] <= _lib.LANE_MAX_PTS:
+            raise CldError(f"lane: polylines must be [L, 2..{_lib.LANE_MAX_PTS}, 3], got {tuple(lines.shape)}")
+        L = int(lines.shape[0])
+        if c.get("validate", True):
+            seen = set()
+            for e, (a, l) in enumerate(zip(ag, ln)):
+                if not (0 <= a < A and 0 <= l < L):
+                    raise CldError(f"lane entry {e}: agent {a} / line {l} outside 0..{A - 1} / 0..{L - 1}")
+                if a in seen and ag[e - 1] != a:
+                    raise CldError(f"lane entry {e}: the entries of agent {a} are not contiguous")
+                seen.add(a)
+        kd = c["kind"]
+        kd = [kd] * E if isinstance(kd, (str, int)) else list(kd.tolist() if isinstance(kd, (torch.Tensor, np.ndarray)) else kd)
+        if len(kd) != E:
+            raise CldError(f"lane kind: expected {E} entries, got {len(kd)}")
+        try:
+            kd = [_lib.LANE_KINDS[k] if isinstance(k, str) else int(k) for k in kd]
+        except KeyError as e:
+            raise CldError(f"lane kind {e.args[0]!r}: one of {sorted(_lib.LANE_KINDS)}") from None
+        if any(k not in _lib.LANE_KINDS.values() for k in kd):
+            raise CldError(f"lane kind: numbers {sorted(_lib.LANE_KINDS.values())}")
+
+        def per_entry(key, default=0.0):
+            v = c.get(key, default)
+            return torch.full((E,), float(v), device=self.device) if np.isscalar(v) else self._f32(torch.as_tensor(v, dtype=torch.float32), (E,))
+        dec = per_entry("decay", 0.9)
+        sc = per_entry("scale") if c.get("scale") is not None else per_entry("weight") / N
+        i32 = lambda v: torch.tensor(v, dtype=torch.int32, device=self.device)
+        agt, lnt, kind = i32(ag), i32(ln), i32(kd)
+        cs = _lib.CldLaneTerm(lines.data_ptr(), agt.data_ptr(), lnt.data_ptr(), kind.data_ptr(), dec.data_ptr(), sc.data_ptr(), E, L,
+                              int(lines.shape[1]), N)
+        return cs, (lines, agt, lnt, kind, dec, sc)
+
+    @contextlib.contextmanager
+    def _lane_term(self, guidance: Optional[Mapping], B: int):
+        """The `lane` entry of a guidance dict kept on the handle for the library call inside (cld_set_lane_term; world-frame
+        polylines are prepared once, here, for the whole call), and cleared behind it whatever happens."""
+        g = None if guidance is None else guidance.get("lane")
+        if g is None:
+            yield
+            return
+        cs, keep = self._lane(g, B)
+        self._check(self.lib.cld_set_lane_term(self._h, C.byref(cs)), "cld_set_lane_term")
+        try:
+            yield
+        finally:
+            self.lib.cld_set_lane_term(self._h, None)
+
+    def lane_loss(self, traj, term: Mapping, grad_in=None, want_grad=True, want_proj=False):
+        """Upstream's lane-projection losses on decoded plans [B,52,6] (descaled, sample-minor rows; `term`: see _lane) -> values
+        [E, num_samp] (unweighted) [, grad_in + d total / d traj [B,52,6]] [, the projections [E, num_samp, 52, 3]]; cld_lane_loss."""
+        traj = self._f32(traj)
+        B = traj.shape[0]
+        traj = self._f32(traj, (B, T, 6))
+        cs, keep = self._lane(term, B)
+        gi = None if grad_in is None else self._f32(grad_in, (B, T, 6))
+        value = torch.empty(cs.num_entries, cs.num_samp, dtype=torch.float32, device=self.device)
+        grad = torch.empty(B, T, 6, dtype=torch.float32, device=self.device) if want_grad else None
+        proj = torch.empty(cs.num_entries, cs.num_samp, T, 3, dtype=torch.float32, device=self.device) if want_proj else None
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cld_lane_loss(self._h, _ptr(traj), C.byref(cs), _ptr(gi), _ptr(value), _ptr(proj), _ptr(grad), B, self._stream()),
+                        "cld_lane_loss")
+        out = (value,) + ((grad,) if want_grad else ()) + ((proj,) if want_proj else ())
+        return out if len(out) > 1 else value
+
     def goal_loss(self, traj, goal: Mapping, grad_in=None, want_grad=True):
         """Upstream's global waypoint losses on decoded plans [B,52,6] (descaled, sample-minor rows; `goal`: see _goal) ->
         (per-row values [B] as upstream files them under guide_losses, grad_in + scale * d value / d traj [B,52,6]); cld_goal_loss."""
@@ -842,7 +963,7 @@ class Engine:
         xn = torch.empty_like(mean) if z is not None else None
         gr = torch.empty_like(mean) if want_grad else None
         ws, wsn = self._workspace(B)
-        with torch.cuda.device(self.device), self._goal_term(guidance, B), self._social_term(guidance, B), self._pair_term(guidance, B), self._map_source_term((guidance or {}).get("map_collision"), B):
+        with torch.cuda.device(self.device), self._goal_term(guidance, B), self._social_term(guidance, B), self._pair_term(guidance, B), self._lane_term(guidance, B), self._map_source_term((guidance or {}).get("map_collision"), B):
             self._check(self.lib.cld_guidance_step(self._h, _ptr(mean), _ptr(cond), C.byref(cg), C.c_float(sigma), _ptr(z),
                                                    _ptr(mg), _ptr(xn), _ptr(gr), B, ws, wsn, self._stream()), "cld_guidance_step")
         out = (mg,) + ((xn,) if z is not None else ()) + ((gr,) if want_grad else ())
@@ -903,7 +1024,7 @@ class Engine:
         x1 = torch.empty_like(x_T) if (want_x1 and 1 in range(0, self.n_timesteps, self.stride)) else None
         logp = torch.empty(B, dtype=torch.float32, device=self.device) if want_logp else None
         cfg = non_cond is not None and guidance_w != 0.0
-        with torch.cuda.device(self.device), self._goal_term(guidance, B), self._social_term(guidance, B), self._pair_term(guidance, B), self._map_source_term((guidance or {}).get("map_collision"), B):
+        with torch.cuda.device(self.device), self._goal_term(guidance, B), self._social_term(guidance, B), self._pair_term(guidance, B), self._lane_term(guidance, B), self._map_source_term((guidance or {}).get("map_collision"), B):
             if guidance is not None:
                 cg, keep = self._guidance(guidance, B)
                 non_cond = self._f32(non_cond, (B, COND)) if cfg else None
@@ -943,7 +1064,7 @@ class Engine:
         gr = torch.empty_like(x_t) if guided and want_grad else None
         ws, wsn = self._workspace(2 * ((B + 15) // 16 * 16) if cfg else B)
         sigma = C.c_float()
-        with torch.cuda.device(self.device), self._goal_term(guidance, B), self._social_term(guidance, B), self._pair_term(guidance, B), self._map_source_term((guidance or {}).get("map_collision"), B):
+        with torch.cuda.device(self.device), self._goal_term(guidance, B), self._social_term(guidance, B), self._pair_term(guidance, B), self._lane_term(guidance, B), self._map_source_term((guidance or {}).get("map_collision"), B):
             self._check(self.lib.cld_sample_step(self._h, _ptr(x_t), _ptr(cond), _ptr(non_cond), C.c_float(guidance_w),
                                                  None if cg is None else C.byref(cg), int(t_idx), _ptr(z), _ptr(xn), _ptr(mean),
                                                  _ptr(mg), _ptr(gr), C.byref(sigma), B, ws, wsn, self._stream()), "cld_sample_step")

@@ -52,7 +52,7 @@ class Action:
         return Action(f(self.positions), f(self.yaws))
 
 
-SCENE_LEVEL_LOSSES = ("agent_collision", "social_group", "gptcollision", "gptkeepdistance")
+SCENE_LEVEL_LOSSES = ("agent_collision", "social_group", "gptcollision", "gptkeepdistance", "gptlanefollowing", "gptchangetoleftlane", "gptfollowlane")
 GOAL_KINDS = {"global_target_pos": 1, "global_target_pos_at_time": 2}       # cld_goal.kind (include/cld.h); per-agent selection: not scene-level
 LOSS_COLUMN = {"target_speed": 0, "speed_limit": 1, "acc_limit": 2, "target_pos_at_time": 3, "target_pos": 3}   # cld_guidance_losses
 
@@ -196,6 +196,24 @@ def refresh_pair_term(g: Optional[Mapping], obs: Mapping):
     return dict(g, pair=dict(g["pair"], world_from_agent=obs["world_from_agent"], agent_from_world=obs.get("agent_from_world")))
 
 
+def refresh_lane_term(g: Optional[Mapping], obs: Mapping):
+    """The guidance dict `g` with its lane term brought to this observation (upstream's get_lane_projection reads the frames and the
+    map at every call, trajdata_utils.py:590-643): agent_from_world from `obs` (or the inverse of its world_from_agent), so that the
+    polylines are taken into the agents' frames of NOW when the term is next prepared, and new world polylines from
+    obs['lane_points'] / ['left_lane_points'] where it carries them (the lane under an agent changes as it drives); nothing is
+    modified in place."""
+    if g is None or g.get("lane") is None or g["lane"].get("world_lines") is None:
+        return g
+    F = obs.get("agent_from_world")
+    if F is None and obs.get("world_from_agent") is not None:
+        F = invert_frames(torch.as_tensor(obs["world_from_agent"]).float())
+    new = {} if F is None else {"agent_from_world": F}
+    sources = g["lane"].get("sources")
+    if sources is not None and all(obs.get(src) is not None for src, _ in sources):
+        new["world_lines"] = gather_lane_lines(obs, sources)
+    return dict(g, lane=dict(g["lane"], **new)) if new else g
+
+
 def refresh_social_term(g: Optional[Mapping], obs: Mapping):
     """The guidance dict `g` with the frames of its social-group term taken from `obs` where it holds them (upstream's loss reads
     data_batch['world_from_agent'] at every call, guidance_loss.py:1156); nothing is modified in place."""
@@ -238,7 +256,10 @@ class CldPolicy:
         follow_observation their frames follow every observation too.  `social_seed` seeds their draws (default 0); every
         get_action moves their evaluation index on, so successive plans do not reuse draws.  The pair-relation configs
         (`gptcollision`, `gptkeepdistance`, ...; pair_terms_from_config) are taken out before them and kept as guidance['pair'];
-        they read world_from_agent (and agent_from_world, when there) of `data_batch` and follow the observation likewise."""
+        they read world_from_agent (and agent_from_world, when there) of `data_batch` and follow the observation likewise.  The lane
+        configs (`gptlanefollowing`, `gptchangetoleftlane`, `gptfollowlane`; lane_terms_from_config) are taken out after the pair
+        configs and kept as guidance['lane']; they read `lane_points` / `left_lane_points` and the frames of `data_batch`, and with
+        follow_observation the polylines are taken into the frames (and from the lanes) of every observation (refresh_lane_term)."""
         data_batch = opt.pop("data_batch", None)         # observation fields scene-coupled losses read (agent_collision: extent, world_from_agent, curr_speed)
         follow = bool(opt.pop("follow_observation", False))
         map_source = opt.pop("map_source", None)
@@ -247,11 +268,14 @@ class CldPolicy:
             raise ValueError(f"goal_reached_by={by!r} (any | own)")
         social_seed = int(opt.pop("social_seed", 0))
         rest, pair = pair_terms_from_config(guidance_config_list, scene_index, data_batch)
+        rest, lane = lane_terms_from_config(rest, scene_index, data_batch)
         rest, social = social_groups_from_config(rest, scene_index, data_batch)
-        peeled = social is not None or pair is not None
+        peeled = social is not None or pair is not None or lane is not None
         base = guidance_from_config(rest, scene_index, data_batch=data_batch, map_source=map_source) if not peeled or any(len(c) for c in rest) else {}
         if pair is not None:
             base["pair"] = pair
+        if lane is not None:
+            base["lane"] = lane
         if social is not None:
             base["social_group"] = dict(social, seed=social_seed)
         self._guidance = dict(base, **opt)
@@ -299,7 +323,9 @@ class CldPolicy:
         vals = (self.vae.engine.guidance_losses(traj.reshape(B * N, 52, 6), g).reshape(B, N, 4) if has_builtin
                 else torch.full((B, N, 4), float("nan"), device=traj.device))
         nan = torch.full((B, N), float("nan"), device=vals.device)
-        colv = mapv = goalv = socv = pairv = None
+        colv = mapv = goalv = socv = pairv = lanev = None
+        if g.get("lane") is not None:                # per (entry, sample), unweighted
+            lanev = self.vae.engine.lane_loss(traj.reshape(B * N, 52, 6), dict(g["lane"], num_samp=N), want_grad=False)
         if g.get("pair") is not None:                # per (pair, sample) as upstream's classes return them (unweighted)
             pairv = self.vae.engine.pair_loss(traj.reshape(B * N, 52, 6), dict(g["pair"], num_samp=N), want_grad=False)
         if g.get("social_group") is not None:        # unweighted per-row values (guidance_loss.py:1205); 0 outside the groups here, NaN below
@@ -325,6 +351,11 @@ class CldPolicy:
                     if c["name"] in PAIR_NAMES:      # the [N] value under EVERY agent of the scene (indiv_loss[agt_mask] = cur_loss, :2171)
                         pv = pairv[g["pair"]["configs"].index((si, gi))]
                         out["%s_scene_%03d_%02d" % (c["name"], si, gi)] = torch.where(mask[:, None], pv[None, :].expand(B, N), nan)
+                        continue
+                    if c["name"] in LANE_NAMES:      # likewise; LaneFollowingLoss: the mean over its targets (:1626)
+                        rows = [e for e, sg in enumerate(g["lane"]["configs"]) if sg == (si, gi)]
+                        lv = lanev[rows].mean(dim=0)
+                        out["%s_scene_%03d_%02d" % (c["name"], si, gi)] = torch.where(mask[:, None], lv[None, :].expand(B, N), nan)
                         continue
                     v = (colv if c["name"] == "agent_collision" else mapv if c["name"] == "map_collision" else
                          goalv if c["name"] in GOAL_KINDS else socv if c["name"] == "social_group" else vals[..., LOSS_COLUMN[c["name"]]])
@@ -361,6 +392,15 @@ class CldPolicy:
                 for p in range(pairv.shape[0]):
                     nm = config_name[kd[p] if isinstance(kd[p], str) else number[int(kd[p])]]
                     out["%s_scene_000_%02d" % (nm, len(names[0]))] = pairv[p][None, :].expand(B, N).clone()
+                    names[0].append(nm)
+            if lanev is not None:                     # one scene: every entry's value under every agent, keyed by the kind's config name
+                number = {v: k for k, v in _lib.LANE_KINDS.items()}
+                config_name = {spec[0]: nm for nm, spec in LANE_NAMES.items()}
+                kd = g["lane"]["kind"]
+                kd = [kd] * lanev.shape[0] if isinstance(kd, (str, int)) else list(kd)
+                for e in range(lanev.shape[0]):
+                    nm = config_name[kd[e] if isinstance(kd[e], str) else number[int(kd[e])]]
+                    out["%s_scene_000_%02d" % (nm, len(names[0]))] = lanev[e][None, :].expand(B, N).clone()
                     names[0].append(nm)
         return out, names
 
@@ -402,7 +442,7 @@ class CldPolicy:
             g = dict(g, guide_clean=True)
         from_cfg = g is self._guidance and self._guidance_cfg is not None
         if guidance is None and self._follow_observation:           # the collision terms of set_guidance follow this observation
-            g = refresh_pair_term(refresh_social_term(refresh_collision_terms(g, obs_dict), obs_dict), obs_dict)
+            g = refresh_lane_term(refresh_pair_term(refresh_social_term(refresh_collision_terms(g, obs_dict), obs_dict), obs_dict), obs_dict)
         if g is not None and g.get("social_group") is not None and guidance is None:
             # the plan's loop iterations take evaluation indices social_iter .. social_iter + loop_steps - 1, the values reported on the
             # final output (below) the one behind them
@@ -470,7 +510,7 @@ def closed_loop_rollout(policy: CldPolicy, cond_fn: Callable, centroid, yaw, cur
     of the previous plan taken into the new agent frame (the last one is the agent's position now), on the first step the current
     position repeated.  `step_index` = the sim step is the goal losses' global_t.
     With collision guidance that follows the observation (`set_guidance(..., follow_observation=True)`) the same holds for
-    `world_from_agent` (from the world pose; a social-group or pair term reads it too), `curr_speed` (`curr_states[:, 2]`) and `world`
+    `world_from_agent` (from the world pose; a social-group, pair or lane term reads it too), `curr_speed` (`curr_states[:, 2]`) and `world`
     [B,3], the pose itself, which a map_collision term in map mode is evaluated at; a raster-mode term needs `drivable_map` from `cond_fn` (SceneObserver gives it).
     Returns the world poses after each sim step [n_sim_steps, B, 3]."""
     import inspect
@@ -506,7 +546,7 @@ def closed_loop_rollout(policy: CldPolicy, cond_fn: Callable, centroid, yaw, cur
                         hw = world[:, None, :2].expand(-1, n_step_action, -1) if hist_world is None else hist_world
                         obs["agent_hist"] = transform_points(hw, torch.as_tensor(obs["agent_from_world"]).float().to(hw.device))
                 pg = policy._guidance or {}
-                if gk is None and policy._follow_observation and any(pg.get(k) is not None for k in ("agent_collision", "map_collision", "social_group", "pair")):
+                if gk is None and policy._follow_observation and any(pg.get(k) is not None for k in ("agent_collision", "map_collision", "social_group", "pair", "lane")):
                     obs = dict(obs)                   # the collision terms follow the observation: what cond_fn's lacks, from the loop's own state
                     if "world_from_agent" not in obs:
                         obs["world_from_agent"] = frames_from_pose(world)
@@ -595,6 +635,96 @@ def pair_terms_from_config(guidance_config_list, scene_index, data_batch: Option
     return rest, term
 
 
+# upstream's lane-projection losses, classes it reaches only through its language-model front end (LaneFollowingLoss,
+# ChangeToLeftLaneLoss, FollowLaneLoss): this project's config name -> (cld_lane_term kind, the data_batch field its polylines come
+# from, the parameter that names the target(s) and upstream's default)
+LANE_NAMES = {
+    "gptlanefollowing": ("following", "lane_points", "target_inds", [1, 2, 3]),
+    "gptchangetoleftlane": ("change_left", "left_lane_points", "target_ind", 6),
+    "gptfollowlane": ("follow_decayed", "lane_points", "target_ind", 4),
+}
+
+
+def gather_lane_lines(data_batch: Mapping, sources):
+    """The world-frame polylines of a lane term: `sources` [(field of data_batch, batch row)] -> [L,S,3] float64 on the CPU, S the
+    widest field's, NaN-padded."""
+    fields = {k: torch.as_tensor(data_batch[k]).detach().to("cpu", torch.float64) for k in {src for src, _ in sources}}
+    S = max(int(v.shape[1]) for v in fields.values())
+    out = torch.full((len(sources), S, 3), float("nan"), dtype=torch.float64)
+    for l, (src, row) in enumerate(sources):
+        v = fields[src]
+        out[l, :v.shape[1]] = v[row]
+    return out
+
+
+def lane_terms_from_config(guidance_config_list, scene_index, data_batch: Optional[Mapping] = None, num_samp: Optional[int] = None):
+    """Upstream's lane-projection configs taken out of a guidance configuration -> (the list without them, the `lane` entry of a
+    guidance dict -- Engine._lane -- or None when there is none).
+
+    Names and parameters (upstream's constructors, guidance_loss.py:1578, 1799, 1962): `gptlanefollowing` (target_inds = [1, 2, 3]:
+    K entries of weight / K, the reported value their mean), `gptchangetoleftlane` (target_ind = 6, on the LEFT lane's polyline),
+    `gptfollowlane` (target_ind = 4, decay_rate = 0.9, T = 52; another T is refused).  The indices are those of the config's scene
+    and are mapped to batch indices here.  The polylines come from data_batch['lane_points'] / ['left_lane_points'] [B_all,S,3]
+    (x, y, heading in the WORLD frame, NaN-padded, S <= 1024): per agent the current (left) lane already concatenated with its
+    successors, as upstream's lines 617-639 would -- choosing the lane is the caller's.  Only targeted rows need be finite.  The
+    term carries the world polylines of the targeted rows (`world_lines`, `sources`), `line_frame`, agent_from_world (from
+    `data_batch`, or the inverse of its world_from_agent) -- Engine._lane prepares them once per call -- and per entry agent, line,
+    kind, decay, `weight` (Engine._lane folds weight / num_samp into the kernel's scale; with `num_samp` given, that `scale` too),
+    `configs` (scene, config index) and `names`; the entries are ordered by agent (stable), as the kernel wants them.
+    ValueError: no frames or no polylines in `data_batch`, an index outside the scene, T != 52, a targeted row without a usable
+    polyline (fewer than two distinct finite points).  NotImplementedError: an `agents` subset."""
+    scene_index = torch.as_tensor(scene_index).reshape(-1).cpu()
+    _, local = torch.unique_consecutive(scene_index, return_inverse=True)
+    rest, entries, sources = [], [], []
+    for si, cfgs in enumerate(guidance_config_list):
+        keep = []
+        for gi, cfg in enumerate(cfgs):
+            if cfg["name"] not in LANE_NAMES:
+                keep.append(cfg)
+                continue
+            kind, field, p_target, d_target = LANE_NAMES[cfg["name"]]
+            if data_batch is None or (data_batch.get("agent_from_world") is None and data_batch.get("world_from_agent") is None):
+                raise ValueError(f"{cfg['name']} needs data_batch with agent_from_world or world_from_agent")
+            if data_batch.get(field) is None:
+                raise ValueError(f"{cfg['name']} needs data_batch['{field}'] [B,S,3]")
+            if cfg.get("agents") is not None:
+                raise NotImplementedError(f"{cfg['name']} on an `agents` subset")
+            prm = cfg.get("params") or {}
+            if kind == "follow_decayed" and int(prm.get("T", 52)) != 52:
+                raise ValueError(f"{cfg['name']}: T = {prm['T']} (only the full horizon, T = 52, is built)")
+            members = torch.nonzero(local == si).reshape(-1)
+            tg = prm.get(p_target, d_target)
+            tg = [int(v) for v in (tg if isinstance(tg, (list, tuple)) else [tg])]
+            if not tg:
+                raise ValueError(f"{cfg['name']}: no target")
+            pts = torch.as_tensor(data_batch[field])
+            if pts.dim() != 3 or pts.shape[0] != scene_index.numel() or pts.shape[2] != 3 or not 2 <= pts.shape[1] <= _lib.LANE_MAX_PTS:
+                raise ValueError(f"{cfg['name']}: data_batch['{field}'] must be [{scene_index.numel()}, 2..{_lib.LANE_MAX_PTS}, 3], got {tuple(pts.shape)}")
+            for v in tg:
+                if not 0 <= v < members.numel():
+                    raise ValueError(f"{cfg['name']}: {p_target} = {v} outside scene {si} of {members.numel()} agents")
+                a = int(members[v])
+                xy = pts[a, :, :2].double()
+                xy = xy[torch.isfinite(xy).all(dim=1)]
+                if xy.shape[0] < 2 or bool((xy == xy[:1]).all()):
+                    raise ValueError(f"{cfg['name']}: agent {v} of scene {si} has no usable polyline in data_batch['{field}']")
+                if (field, a) not in sources:
+                    sources.append((field, a))
+                entries.append(dict(agent=a, line=sources.index((field, a)), kind=kind, decay=float(prm.get("decay_rate", 0.9)),
+                                    weight=float(cfg["weight"]) / len(tg), configs=(si, gi), names=cfg["name"]))
+        rest.append(keep)
+    if not entries:
+        return rest, None
+    entries.sort(key=lambda e: e["agent"])                                # (stable: an agent's entries keep the configs' order)
+    F = data_batch.get("agent_from_world")
+    term = {k: [e[k] for e in entries] for k in ("agent", "line", "kind", "decay", "weight", "configs", "names")}
+    term.update(world_lines=gather_lane_lines(data_batch, sources), sources=sources, line_frame=[a for _, a in sources],
+                agent_from_world=F if F is not None else invert_frames(torch.as_tensor(data_batch["world_from_agent"]).float()))
+    if num_samp is not None:
+        term["scale"] = [w / int(num_samp) for w in term["weight"]]
+    return rest, term
+
+
 def social_groups_from_config(guidance_config_list, scene_index, data_batch: Optional[Mapping] = None):
     """Upstream's `social_group` configs (SocialGroupLoss, guidance_loss.py:1137-1207) taken out of a guidance configuration ->
     (the list without them, the `social_group` entry of a guidance dict -- Engine._social -- or None when there is none).
@@ -660,7 +790,7 @@ def guidance_from_config(guidance_config_list, scene_index, horizon: int = 52, d
     weight / agents; at most one per agent, one dt and one min_progress_dist per call); at most
     one of each other loss per scene, one parameter set per call; the others (stop signs, lane keeping, ...) are not built, and
     `social_group` is refused HERE too: it is scene-coupled and random, and enters one level up (social_groups_from_config, which
-    CldPolicy.set_guidance calls first); so do the pair-relation names (`gptcollision`, `gptkeepdistance`, ...: pair_terms_from_config).  One speed / acceleration limit value per call."""
+    CldPolicy.set_guidance calls first); so do the pair-relation names (`gptcollision`, `gptkeepdistance`, ...: pair_terms_from_config) and the lane names (`gptlanefollowing`, ...: lane_terms_from_config).  One speed / acceleration limit value per call."""
     scene_index = torch.as_tensor(scene_index).reshape(-1).cpu()
     B = scene_index.numel()
     _, local = torch.unique_consecutive(scene_index, return_inverse=True)
