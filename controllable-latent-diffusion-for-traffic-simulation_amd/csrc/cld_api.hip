@@ -1467,7 +1467,8 @@ static int check_collision(cld_handle h, const char* fn, const cld_collision* c,
     if (!c->extent || !c->world_from_agent || !c->curr_speed || !c->scene_start) return fail(h, CLD_ERR_ARG, std::string(fn) + ": collision term: null pointer");
     if (c->num_scenes < 1 || c->num_samp < 1 || B % c->num_samp) return fail(h, CLD_ERR_ARG, std::string(fn) + ": collision term: B must be agents x num_samp, num_scenes >= 1");
     if (c->num_disks < 1 || c->num_disks > 8) return fail(h, CLD_ERR_ARG, std::string(fn) + ": collision term: num_disks must be 1..8");
-    if (c->max_scene_agents < 1 || c->max_scene_agents > 150) return fail(h, CLD_ERR_ARG, std::string(fn) + ": collision term: scenes of 1..150 agents");
+    // 192: the largest scene whose poses fit launch_agent_collision's 160-KiB LDS request (163,664 B; 193 agents would need 164,512)
+    if (c->max_scene_agents < 1 || c->max_scene_agents > 192) return fail(h, CLD_ERR_ARG, std::string(fn) + ": collision term: scenes of 1..192 agents");
     return CLD_OK;
 }
 

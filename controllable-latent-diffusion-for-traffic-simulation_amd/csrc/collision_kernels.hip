@@ -6,11 +6,11 @@
 // masks it down to the pairs of one scene.  Here a workgroup owns four agents of one (scene, sample): the world poses of ALL the
 // scene's agents at all 52 steps sit in its LDS (16 B per pose; every workgroup of the scene re-derives them from the plans --
 // 3,328 sincos / atan2 for a 64-agent scene, far cheaper than a second launch), one thread per (own agent, step) walks the other
-// agents of the scene, rejects far pairs on the centre distance (exact: a disk centre lies within length / 2 - radius of the
-// agent's centre) and evaluates the 25 disk pairs of the rest; an agent's 52 per-step sums stay inside one workgroup, so its
-// value is added up in a fixed order (deterministic, no atomics).  A 64-agent scene is 16 workgroups, BASELINE configs[2]'s 32
-// scenes 512: the first form of this kernel (one workgroup per scene) took 880 us there.  Value and gradient come out of the
-// same pass: the loss is
+// agents of the scene, rejects far pairs on the centre distance (exact: a disk centre lies within |length / 2 - radius| of the
+// agent's centre; that half extent is negative for an agent wider than long) and evaluates the 25 disk pairs of the rest; an
+// agent's 52 per-step sums stay inside one workgroup, so its value is added up in a fixed order (deterministic, no atomics).  A
+// 64-agent scene is 16 workgroups, BASELINE configs[2]'s 32 scenes 512: the first form of this kernel (one workgroup per scene)
+// took 880 us there.  Value and gradient come out of the same pass: the loss is
 //     value[i] = [moving_i] sum_t w_t (1 / B) sum_j pen_ij(t),  pen = 1 - d_ij / (r_i + r_j + buffer)  where d_ij <= that bound,
 //     total    = sum_scenes weight_s * mean over the scene's guided agents (and samples) of value   (DiffuserGuidance, :2143-2172),
 // pen is symmetric in (i, j), agents that are stationary or not guided are detached (:512-534), so
@@ -89,9 +89,12 @@ __global__ __launch_bounds__(256) void agent_collision_kernel(const CollisionArg
     }
     __syncthreads();
 
-    // normalised step weights decay^t / sum (:614-616)
-    float wsum = 0.f, wp = 1.f;
-    for (int t = 0; t < TT; ++t) { wsum += wp; wp *= p.decay_rate; }
+    // normalised step weights decay^t / sum (:614-616), formed in double and rounded once: a float running product is off by t roundings
+    // at step t and, with a float sum over the 52 steps, left the values 3e-7 (relative) from float64 -- above what upstream's own
+    // float32 evaluation differs by when the geometry repeats from step to step (tests/test_gpu_collision_regimes.py, kink_*)
+    const double dec = (double)p.decay_rate;
+    double wsum = 0.0, wp = 1.0;
+    for (int t = 0; t < TT; ++t) { wsum += wp; wp *= dec; }
     const int D = p.num_disks;
     const float inv_b = 1.0f / (float)p.B_agents;
     const float coef = (n_guided > 0 && wgt != 0.f) ? wgt / ((float)n_guided * (float)p.num_samp * (float)p.B_agents) : 0.f;
@@ -102,7 +105,9 @@ __global__ __launch_bounds__(256) void agent_collision_kernel(const CollisionArg
         const float4 pi = pose[it];
         const float ri = agent[i * 4 + 0], ei = agent[i * 4 + 1], acti = agent[i * 4 + 2];
         const bool excl_i = ((int)agent[i * 4 + 3] & 2) != 0;
-        const float wt = powf(p.decay_rate, (float)t) / wsum;
+        double wpt = 1.0;
+        for (int k = 0; k < t; ++k) wpt *= dec;
+        const float wt = (float)(wpt / wsum);
         float cxi[kMaxDisks];
 #pragma unroll
         for (int a = 0; a < kMaxDisks; ++a) cxi[a] = disk_centre(ei, a, D);
@@ -114,7 +119,7 @@ __global__ __launch_bounds__(256) void agent_collision_kernel(const CollisionArg
             const float rj = agent[j * 4 + 0], ej = agent[j * 4 + 1];
             const float pd = ri + rj + p.buffer_dist;
             const float dx = pi.x - pj.x, dy = pi.y - pj.y;
-            const float reach = pd + ei + ej + 1e-3f;
+            const float reach = pd + fabsf(ei) + fabsf(ej) + 1e-3f;     // |.|: a pedestrian of 0.6 x 0.7 m has ei = -0.05
             if (dx * dx + dy * dy > reach * reach) continue;       // no disk pair can be within pd
             float best = 3.0e38f, bdx = 0.f, bdy = 0.f, bcx = 0.f;
             for (int a = 0; a < D; ++a) {
@@ -160,9 +165,9 @@ __global__ __launch_bounds__(256) void agent_collision_kernel(const CollisionArg
     if (p.loss) {
         for (int io = tid; io < own / TT; io += 256) {
             const int i = i0 + io;
-            float v = 0.f;
-            for (int t = 0; t < TT; ++t) v += part[io * TT + t];   // fixed order: deterministic
-            p.loss[(size_t)(a0 + i) * p.num_samp + n] = ((int)agent[i * 4 + 3] & 1) ? v : 0.f;
+            double v = 0.0;
+            for (int t = 0; t < TT; ++t) v += (double)part[io * TT + t];   // fixed order: deterministic
+            p.loss[(size_t)(a0 + i) * p.num_samp + n] = ((int)agent[i * 4 + 3] & 1) ? (float)v : 0.f;
         }
     }
 }
@@ -172,7 +177,7 @@ hipError_t launch_agent_collision(const CollisionArgs& a, hipStream_t s) {
     const int max_scene_agents = a.max_scene_agents;
     if (a.num_disks < 1 || a.num_disks > kMaxDisks || a.num_scenes < 1 || a.num_samp < 1 || max_scene_agents < 1) return hipErrorInvalidValue;
     const size_t lds_bytes = ((size_t)max_scene_agents * TT * 4 + (size_t)kOwn * TT + (size_t)max_scene_agents * 4 + 4) * sizeof(float);
-    if (lds_bytes > 160 * 1024) return hipErrorInvalidValue;          // a scene of more than ~190 agents: not built
+    if (lds_bytes > 160 * 1024) return hipErrorInvalidValue;          // a scene of more than 192 agents: not built
     static unsigned long long attr_done = 0;      // one bit per device (a second handle on another device sets it there too)
     if (hipError_t e = set_max_lds_once(reinterpret_cast<const void*>(agent_collision_kernel), 160 * 1024, &attr_done); e != hipSuccess) return e;
     hipLaunchKernelGGL(agent_collision_kernel, dim3(a.num_scenes * a.num_samp, (max_scene_agents + kOwn - 1) / kOwn), dim3(256), lds_bytes, s, a);

@@ -255,7 +255,7 @@ typedef struct cld_collision {
     int32_t num_scenes;
     int32_t num_samp;
     int32_t num_disks;              /* 1..8 (upstream default 5)                                                            */
-    int32_t max_scene_agents;       /* largest scene_start[s + 1] - scene_start[s] (sizes the kernel's LDS; <= 150)         */
+    int32_t max_scene_agents;       /* largest scene_start[s + 1] - scene_start[s] (sizes the kernel's LDS; <= 192)         */
     float buffer_dist;              /* upstream default 0.2                                                                 */
     float decay_rate;               /* 0.9                                                                                  */
     float moving_speed_th;          /* 0.5                                                                                  */
