@@ -1,4 +1,4 @@
-"""ctypes binding of libcld_hip.so (C-ABI: include/cld.h).
+"""ctypes binding of libcld_hip.so (C-ABI: include/cld.h, include/cld_lane.h, include/cld_eval.h).
 
 The product path has NO fallback: if the HIP library is missing or a call
 fails, a `CldError` is raised.  Nothing under `oracle/` is ever imported here.
@@ -295,6 +295,20 @@ LANE_SIGNATURES = {
     "cld_set_lane_term": (C.c_int, [_P, C.POINTER(CldLaneTerm)]),
 }
 
+# name -> (restype, argtypes); every symbol include/cld_eval.h declares (the open-loop sample metrics; a third table of its own)
+EVAL_SIGNATURES = {
+    "cld_sample_metrics_workspace_bytes": (C.c_size_t, [C.c_int32]),
+    "cld_sample_metrics": (C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_size_t, _P]),
+    "cld_debug_sample_metrics_max_blocks": (C.c_int32, []),
+}
+# include/cld_eval.h CLD_SM_*: the columns of a per-agent row of cld_sample_metrics; the first eight under upstream's keys
+# (DiffuserTrafficModel._compute_metrics), the last two this library's last-step pair distance
+SAMPLE_METRIC_COLS = ("ego_avg_ADE", "ego_min_ADE", "ego_avg_FDE", "ego_min_FDE", "ego_avg_APD", "ego_max_APD", "ego_avg_FPD", "ego_max_FPD",
+                      "ego_avg_last_step_PD", "ego_max_last_step_PD")
+SAMPLE_METRIC_INDEX = ("best_ade", "best_fde", "last", "nonfinite")      # the columns of its int32 index rows
+SAMPLE_METRICS_MAX_SAMPLES = 256       # include/cld_eval.h CLD_SM_MAX_SAMPLES
+SAMPLE_METRICS_MAX_POINTS = 8192       # include/cld_eval.h CLD_SM_MAX_POINTS
+
 _lib = None
 
 
@@ -312,7 +326,7 @@ def load():
     # library first would pull /opt/rocm's runtime in beside torch's and break device init.
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
-    for table in (SIGNATURES, LANE_SIGNATURES):
+    for table in (SIGNATURES, LANE_SIGNATURES, EVAL_SIGNATURES):
         for name, (res, args) in table.items():
             fn = getattr(lib, name)      # AttributeError if the library does not export it
             fn.restype, fn.argtypes = res, args

@@ -11,9 +11,11 @@
 #include <vector>
 
 #include "../../include/cld.h"
+#include "../../include/cld_eval.h"
 #include "../../include/cld_lane.h"
 #include "cld_kernels.h"
 #include "lane_kernels.h"
+#include "sample_metrics_kernels.h"
 #include "train.h"
 
 using namespace cld;
@@ -2487,6 +2489,32 @@ int cld_realism_terms(cld_handle h, const float* sa, int64_t M, int32_t T, float
     if (M < 1 || T < 2 || M > SORT_MAX_N / T) return fail(h, CLD_ERR_ARG, "cld_realism_terms: needs M >= 1, T >= 2 and M T <= 2^30");
     if (!(dt > 0.f) || !(dt < INFINITY)) return fail(h, CLD_ERR_ARG, "cld_realism_terms: dt must be positive and finite");
     HIPCK(h, launch_realism_terms(sa, M, T, dt, lon, lat, jerk, static_cast<hipStream_t>(stream)));
+    return CLD_OK;
+}
+
+/* ---- open-loop sample metrics: ADE / FDE and diversity (sample_metrics_kernels.hip; include/cld_eval.h) ---- */
+static_assert(CLD_SM_COLS == kSmCols && CLD_SM_MAX_SAMPLES == kSmMaxN && CLD_SM_MAX_POINTS == kSmMaxNT, "cld_eval.h and sample_metrics_kernels.h");
+
+int32_t cld_debug_sample_metrics_max_blocks(void) { return kSmMaxBlocks; }
+
+size_t cld_sample_metrics_workspace_bytes(int32_t B) { return B < 1 || B > kSmMaxB ? 0 : sm_fold_tiles(B) * kSmCols * sizeof(double); }
+
+int cld_sample_metrics(cld_handle h, const float* pred, int32_t C, const float* gt, const float* avail, int32_t B, int32_t N, int32_t T,
+                       double* per_agent, int32_t* index, double* means, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!h) return CLD_ERR_ARG;
+    if (!pred || !gt || !avail || !per_agent || !index) return fail(h, CLD_ERR_ARG, "cld_sample_metrics: null pointer");
+    if (B < 1 || B > kSmMaxB) return fail(h, CLD_ERR_ARG, "cld_sample_metrics: B out of range [1, 2^20]");
+    if (N < 1 || T < 1) return fail(h, CLD_ERR_ARG, "cld_sample_metrics: N and T must be at least 1");
+    if (C < 2 || C > 8) return fail(h, CLD_ERR_ARG, "cld_sample_metrics: C must be 2 .. 8 (channels 0 and 1 are the positions)");
+    if (N > kSmMaxN || (int64_t)N * T > kSmMaxNT)
+        return fail(h, CLD_ERR_ARG, "cld_sample_metrics: N = " + std::to_string(N) + ", T = " + std::to_string(T) + " is beyond N <= " +
+                                        std::to_string(kSmMaxN) + ", N T <= " + std::to_string(kSmMaxNT) + " (an agent's samples are staged in LDS)");
+    if (reinterpret_cast<uintptr_t>(per_agent) % 8 || reinterpret_cast<uintptr_t>(means) % 8)
+        return fail(h, CLD_ERR_ARG, "cld_sample_metrics: per_agent and means must be 8-byte aligned");
+    if (means && (!workspace || workspace_bytes < cld_sample_metrics_workspace_bytes(B) || reinterpret_cast<uintptr_t>(workspace) % 8))
+        return fail(h, CLD_ERR_WORKSPACE, "cld_sample_metrics: workspace missing, misaligned or too small");
+    SampleMetricsArgs a{pred, gt, avail, per_agent, index, B, N, T, C};
+    HIPCK(h, launch_sample_metrics(a, means, static_cast<double*>(workspace), static_cast<hipStream_t>(stream)));
     return CLD_OK;
 }
 

@@ -1691,6 +1691,39 @@ class Engine:
                                                    self._stream()), "cld_realism_terms")
         return out
 
+    # ------------------------------------------------------------------ open-loop sample metrics (tbsim/utils/metrics.py:201-358)
+    def sample_metrics(self, pred, gt, avail, out=None):
+        """ADE / FDE and the diversity of N sampled futures per agent (cld_sample_metrics; include/cld_eval.h defines every column).
+        pred [B,N,T,2] positions or [B,N,T,C <= 8] with the positions in channels 0 and 1 (the [.,.,52,6] tensor `decode` returns is read
+        in place); gt [B,T,2]; avail [B,T], bool or float (converted to fp32).  Confidences are uniform, as upstream passes them.
+        -> {"per_agent": [B,10] float64, "index": [B,4] int32 (best_ade, best_fde, last, nonfinite), "means": [10] float64}, device
+        tensors in the column order of `_lib.SAMPLE_METRIC_COLS`.  `out`: (per_agent, index) contiguous device tensors of at least B
+        rows to write into (float64 [.,10], int32 [.,4]).  N > 256 or N T > 8,192 raises: there is no other path.  No host
+        synchronisation."""
+        pred = self._f32(pred)
+        if pred.dim() != 4 or min(pred.shape) < 1 or not 2 <= pred.shape[3] <= 8:
+            raise CldError(f"sample_metrics: pred must be [B,N,T,C] with 2 <= C <= 8, got {tuple(pred.shape)}")
+        B, N, T, Cc = (int(v) for v in pred.shape)
+        gt = self._f32(gt, (B, T, 2))
+        avail = self._f32(avail, (B, T))
+        cols = len(_lib.SAMPLE_METRIC_COLS)
+        if out is None:
+            rows = torch.empty(B, cols, dtype=torch.float64, device=self.device)
+            index = torch.empty(B, 4, dtype=torch.int32, device=self.device)
+        else:
+            rows, index = out
+            for o, dt, w in ((rows, torch.float64, cols), (index, torch.int32, 4)):
+                if not (isinstance(o, torch.Tensor) and o.device == self.device and o.dtype == dt and o.is_contiguous() and o.dim() == 2
+                        and o.shape[1] == w and o.shape[0] >= B):
+                    raise CldError(f"sample_metrics: out must be contiguous (float64 [>= {B},{cols}], int32 [>= {B},4]) on {self.device}")
+            rows, index = rows[:B], index[:B]
+        means = torch.empty(cols, dtype=torch.float64, device=self.device)
+        ws, wsn = self._scratch("_rws", int(self.lib.cld_sample_metrics_workspace_bytes(B)))
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cld_sample_metrics(self._h, _ptr(pred), Cc, _ptr(gt), _ptr(avail), B, N, T, _ptr(rows), _ptr(index),
+                                                    _ptr(means), ws, wsn, self._stream()), "cld_sample_metrics")
+        return {"per_agent": rows, "index": index, "means": means}
+
     # ------------------------------------------------------------------ measurement
     def profile_enable(self, on: bool = True):
         self._check(self.lib.cld_profile_enable(self._h, int(on)), "cld_profile_enable")

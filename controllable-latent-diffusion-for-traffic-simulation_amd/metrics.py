@@ -18,6 +18,10 @@ ground truth and prediction of three quantities, accumulated and evaluated on th
 `GuidanceMetrics` says whether the guidance worked: upstream's guidance satisfaction metrics (src/tbsim/utils/guidance_metrics.py), one
 to three per entry of the guidance config `set_guidance` takes, under upstream's keys `guide_<metric>_s<scene>g<config>`; one launch per
 environment step (`cld_guide_metrics_step` / `cld_guide_metrics_read`; csrc/guide_metrics_kernels.hip).
+
+`SampleMetrics` is the open-loop side: the ADE / FDE / APD / FPD keys upstream validates its diffusion model with
+(DiffuserTrafficModel._compute_metrics, src/tbsim/algos/algos.py:1818-1852), per agent and as batch means in fp64 (`cld_sample_metrics`;
+csrc/sample_metrics_kernels.hip, include/cld_eval.h).
 """
 from __future__ import annotations
 
@@ -654,3 +658,91 @@ class GuidanceMetrics:
             raise KeyError(f"GuidanceMetrics.per_member: no metric {key!r} (one of {self.keys})")
         e = self._index[key]
         return self.engine.guide_metrics_read(self._setup, self.state)[1][self._member_start[e]:self._member_start[e + 1]]
+
+
+class SampleMetrics:
+    """The open-loop sample metrics upstream validates its diffusion model with (DiffuserTrafficModel._compute_metrics,
+    src/tbsim/algos/algos.py:1818-1852, through src/tbsim/utils/metrics.py:201-358) on the device: how close the N sampled futures of
+    an agent come to the logged one (ADE, FDE: mean over the samples and best sample) and how far they lie apart (APD, FPD: mean and
+    max over all pairs).  include/cld_eval.h defines every column; the per-agent arithmetic is fp64 in `cld_sample_metrics`.
+
+    Two things are upstream's and are reproduced as they are: a mean over time divides by T, not by the number of available steps; and
+    FPD (`batch_final_diversity`) takes the last COORDINATE, y, and the norm over time -- not the distance at the last time step its
+    docstring describes.  That distance is kept beside it as `ego_avg_last_step_PD` / `ego_max_last_step_PD`, keys of this library.
+    Confidences are uniform (1 / N), as upstream passes them; nothing else is built.
+
+    `add` appends the batch's per-agent rows to a grow-by-doubling device buffer (`capacity` rows before it first grows); the fill
+    count follows from the shapes and lives on the host, so `add` issues no synchronisation.  Upstream's `_compute_metrics` covers one
+    batch: that is `last_batch()`; `compute()` covers every agent added since `reset()`."""
+
+    KEYS = _lib.SAMPLE_METRIC_COLS
+    UPSTREAM_KEYS = _lib.SAMPLE_METRIC_COLS[:8]
+
+    def __init__(self, engine, capacity: int = 0):
+        self.engine = engine
+        cap = max(int(capacity), 0)
+        self._rows = torch.empty(cap, len(self.KEYS), dtype=torch.float64, device=engine.device)
+        self._index = torch.empty(cap, 4, dtype=torch.int32, device=engine.device)
+        self._fill = 0
+        self._last = None
+
+    def reset(self):
+        """Forget the rows (the buffers' memory is kept)."""
+        self._fill = 0
+        self._last = None
+
+    def add(self, pred, gt, avail):
+        """One batch: pred [B,N,T,2] (or [B,N,T,6], positions in channels 0 and 1), gt [B,T,2], avail [B,T] bool or float.  N and T may
+        differ between batches.  The kernel writes straight into the buffers' tails."""
+        B, fill = int(pred.shape[0]), self._fill
+        if fill + B > self._rows.shape[0]:
+            cap = max(2 * self._rows.shape[0], fill + B)
+            for name in ("_rows", "_index"):
+                old = getattr(self, name)
+                grown = torch.empty(cap, old.shape[1], dtype=old.dtype, device=old.device)
+                grown[:fill].copy_(old[:fill])
+                setattr(self, name, grown)
+        self._last = self.engine.sample_metrics(pred, gt, avail, out=(self._rows[fill:], self._index[fill:]))["means"]
+        self._fill = fill + B
+
+    def per_agent(self):
+        """-> [M,10] float64: the rows of every agent added since `reset()`, in the order added (a view; columns = `KEYS`)."""
+        return self._rows[:self._fill]
+
+    def index(self):
+        """-> [M,4] int32 (a view): per agent the best sample by ADE, the best by FDE (the first among equals), the last available
+        step (0 when none is) and the non-finite flag."""
+        return self._index[:self._fill]
+
+    def _refuse_nonfinite(self, what: str):
+        bad = torch.nonzero(self.index()[:, 3]).reshape(-1)
+        if bad.numel():
+            raise ValueError(f"SampleMetrics.{what}: non-finite input at {bad.numel()} of {self._fill} agents (first: row {int(bad[0])}); "
+                             f"upstream asserts finiteness")
+
+    def compute(self):
+        """-> {key: 0-d float64 device tensor}: upstream's eight keys and the two last-step ones, each the mean of its column over every
+        agent added since `reset()` (an fp64 sum of the device rows).  ValueError when nothing was added or an agent's non-finite flag
+        is set (this reads the flags back: the one synchronisation)."""
+        if self._fill == 0:
+            raise ValueError("SampleMetrics.compute: nothing was added")
+        self._refuse_nonfinite("compute")
+        means = self.per_agent().sum(dim=0) / float(self._fill)
+        return {k: means[c] for c, k in enumerate(self.KEYS)}
+
+    def last_batch(self):
+        """-> upstream's eight keys for the last batch added alone (0-d float64 device tensors): what `_compute_metrics` returns.  The
+        batch means come from the library's fixed-order fold.  No synchronisation, no finiteness check."""
+        if self._last is None:
+            raise ValueError("SampleMetrics.last_batch: nothing was added")
+        return {k: self._last[c] for c, k in enumerate(self.UPSTREAM_KEYS)}
+
+
+def compute_sample_metrics(engine, pred_batch, data_batch):
+    """`DiffuserTrafficModel._compute_metrics(pred_batch, data_batch)` on the device: pred_batch["predictions"]["positions"] [B,N,T,2],
+    data_batch["target_positions"] [B,T,2], data_batch["target_availabilities"] [B,T] -> upstream's eight keys as 0-d float64 device
+    tensors.  ValueError on non-finite input, where upstream's `_assert_shapes` asserts."""
+    m = SampleMetrics(engine, capacity=int(pred_batch["predictions"]["positions"].shape[0]))
+    m.add(pred_batch["predictions"]["positions"], data_batch["target_positions"], data_batch["target_availabilities"])
+    m._refuse_nonfinite("compute_sample_metrics")
+    return m.last_batch()
