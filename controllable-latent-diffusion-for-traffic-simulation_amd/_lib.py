@@ -1,4 +1,4 @@
-"""ctypes binding of libcld_hip.so (C-ABI: include/cld.h, include/cld_lane.h, include/cld_eval.h).
+"""ctypes binding of libcld_hip.so (C-ABI: include/cld.h, include/cld_lane.h, include/cld_recon.h, include/cld_eval.h).
 
 The product path has NO fallback: if the HIP library is missing or a call
 fails, a `CldError` is raised.  Nothing under `oracle/` is ever imported here.
@@ -295,6 +295,22 @@ LANE_SIGNATURES = {
     "cld_set_lane_term": (C.c_int, [_P, C.POINTER(CldLaneTerm)]),
 }
 
+class CldRecon(C.Structure):
+    """include/cld_recon.h `cld_recon` (the flat U-Net buffer and the step settings of reconstruction guidance)."""
+    _fields_ = [("params", C.c_void_p), ("lr", C.c_float), ("perturb_th", C.c_float), ("descend", C.c_int32)]
+
+
+# name -> (restype, argtypes); every symbol include/cld_recon.h declares (a table of its own, as the lane table)
+RECON_SIGNATURES = {
+    "cld_recon_workspace_bytes": (C.c_size_t, [_P, C.c_int32, C.c_int32]),
+    "cld_recon_step": (C.c_int, [_P, _P, _P, _P, C.c_float, C.POINTER(CldGuidance), C.POINTER(CldRecon), C.c_int32, _P, _P, _P, _P, _P, _P,
+                                 C.POINTER(C.c_float), C.c_int32, C.c_uint64, C.c_uint64, _P, C.c_size_t, _P]),
+    "cld_sample_recon": (C.c_int, [_P, _P, _P, _P, _P, C.c_float, C.POINTER(CldGuidance), C.POINTER(CldRecon), C.c_int32, _P, _P, _P,
+                                   C.c_int32, C.c_uint64, _P, C.c_size_t, _P]),
+    "cld_recon_get_posterior": (C.c_int, [_P, _P, _P]),
+    "cld_debug_recon_grid_cap": (C.c_int32, [C.c_int32]),
+}
+
 # name -> (restype, argtypes); every symbol include/cld_eval.h declares (the open-loop sample metrics; a third table of its own)
 EVAL_SIGNATURES = {
     "cld_sample_metrics_workspace_bytes": (C.c_size_t, [C.c_int32]),
@@ -326,7 +342,7 @@ def load():
     # library first would pull /opt/rocm's runtime in beside torch's and break device init.
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
-    for table in (SIGNATURES, LANE_SIGNATURES, EVAL_SIGNATURES):
+    for table in (SIGNATURES, LANE_SIGNATURES, RECON_SIGNATURES, EVAL_SIGNATURES):
         for name, (res, args) in table.items():
             fn = getattr(lib, name)      # AttributeError if the library does not export it
             fn.restype, fn.argtypes = res, args

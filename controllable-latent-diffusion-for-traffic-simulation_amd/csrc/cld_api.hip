@@ -13,8 +13,10 @@
 #include "../../include/cld.h"
 #include "../../include/cld_eval.h"
 #include "../../include/cld_lane.h"
+#include "../../include/cld_recon.h"
 #include "cld_kernels.h"
 #include "lane_kernels.h"
+#include "recon_kernels.h"
 #include "sample_metrics_kernels.h"
 #include "train.h"
 
@@ -69,6 +71,7 @@ struct cld_handle_s {
     std::vector<void*> dev_allocs;
     // schedule (host, fp32 as in dm_model.py:29-56)
     std::vector<float> x_t_cof, noise_cof, plvc, sqrt_acp, sqrt_1m_acp, sqrt_recip_acp, sqrt_recipm1_acp;
+    std::vector<float> post_coef1, post_coef2;       // posterior_mean_coef1 / 2 (dm_model.py:50-53; the reconstruction-guided step, cld_recon.h)
     float* qs_tab = nullptr;            // device [2][n_timesteps]: sqrt(alphas_cumprod), sqrt(1 - alphas_cumprod) (q_sample, dm_model.py:91-96)
     // device-side model
     ResBlock blocks[12];
@@ -196,7 +199,7 @@ void build_schedule(cld_handle h) {
     double run = 1.0;
     for (int i = 0; i < n; ++i) { run *= (double)alphas[i]; acp[i] = (float)run; acp_prev[i] = i ? acp[i - 1] : 1.0f; }
     h->x_t_cof.resize(n); h->noise_cof.resize(n); h->plvc.resize(n); h->sqrt_acp.resize(n); h->sqrt_1m_acp.resize(n);
-    h->sqrt_recip_acp.resize(n); h->sqrt_recipm1_acp.resize(n);
+    h->sqrt_recip_acp.resize(n); h->sqrt_recipm1_acp.resize(n); h->post_coef1.resize(n); h->post_coef2.resize(n);
     for (int i = 0; i < n; ++i) {
         h->sqrt_acp[i] = std::sqrt(acp[i]);                 // dm_model.py:36-37
         h->sqrt_1m_acp[i] = std::sqrt(1.0f - acp[i]);
@@ -206,6 +209,9 @@ void build_schedule(cld_handle h) {
         h->plvc[i] = (float)std::log((double)(pv < 1e-20f ? 1e-20f : pv));      // correctly rounded: equals torch.log on every entry of the n = 10 / 50 / 100 tables
         h->x_t_cof[i] = std::sqrt(1.0f / alphas[i]);
         h->noise_cof[i] = betas[i] / std::sqrt(alphas[i] - acp[i] * alphas[i]);
+        // dm_model.py:50-53, from the fp32 tables above in double, rounded once
+        h->post_coef1[i] = (float)((double)betas[i] * std::sqrt((double)acp_prev[i]) / (1.0 - (double)acp[i]));
+        h->post_coef2[i] = (float)((1.0 - (double)acp_prev[i]) * std::sqrt((double)alphas[i]) / (1.0 - (double)acp[i]));
     }
 }
 
@@ -2663,6 +2669,191 @@ int cld_vae_decode_backward(cld_handle h, const float* params, const float* z, c
     if (accumulate != 0 && accumulate != 1) return fail(h, CLD_ERR_ARG, "cld_vae_decode_backward: accumulate must be 0 or 1");
     HIPCK(h, vae_train_backward(1, params, z, cond, drop_mask, tape, d_act, nullptr, d_params, dz, dcond, accumulate, B,
                                 static_cast<float*>(workspace), static_cast<hipStream_t>(stream)));
+    return CLD_OK;
+}
+
+/* ---- reconstruction guidance (include/cld_recon.h; recon_kernels.hip) ---- */
+// The step's own buffers behind the sampler workspace: rows Bn = B, or 2 B with CFG ([0, B) conditional, [B, 2 B) unconditional).
+struct ReconWs {
+    float *xt, *cond2, *eps, *deps, *dx, *x0, *g0, *tape, *tws;
+    int32_t* tidx;
+};
+static size_t recon_al(size_t floats) { return (floats + 63) / 64 * 64; }
+static size_t recon_sampler_bytes(cld_handle h, int B, bool cfg) {
+    return (cld_workspace_bytes(h, cfg ? 2 * pad16(B) : B) + 255) / 256 * 256;
+}
+static size_t recon_own_floats(int B, bool cfg) {
+    const size_t bn = cfg ? 2 * (size_t)B : (size_t)B;
+    return 4 * recon_al(bn * T * D) + recon_al(bn * 256) + recon_al(bn) + 2 * recon_al((size_t)B * T * D) + recon_al(train_tape_floats((int)bn)) +
+           recon_al(train_ws_floats((int)bn));
+}
+static ReconWs recon_carve(cld_handle h, void* ws, int B, bool cfg) {
+    const size_t bn = cfg ? 2 * (size_t)B : (size_t)B;
+    float* p = reinterpret_cast<float*>(static_cast<char*>(ws) + recon_sampler_bytes(h, B, cfg));
+    ReconWs r;
+    r.xt = p; p += recon_al(bn * T * D);
+    r.eps = p; p += recon_al(bn * T * D);
+    r.deps = p; p += recon_al(bn * T * D);
+    r.dx = p; p += recon_al(bn * T * D);
+    r.cond2 = p; p += recon_al(bn * 256);
+    r.tidx = reinterpret_cast<int32_t*>(p); p += recon_al(bn);
+    r.x0 = p; p += recon_al((size_t)B * T * D);
+    r.g0 = p; p += recon_al((size_t)B * T * D);
+    r.tape = p; p += recon_al(train_tape_floats((int)bn));
+    r.tws = p;
+    return r;
+}
+
+size_t cld_recon_workspace_bytes(cld_handle h, int32_t B, int32_t cfg) {
+    if (!h || B < 1 || B > (1 << 19)) return 0;
+    return recon_sampler_bytes(h, B, cfg != 0) + recon_own_floats(B, cfg != 0) * sizeof(float);
+}
+
+int cld_recon_get_posterior(cld_handle h, float* coef1, float* coef2) {
+    if (!h) return CLD_ERR_ARG;
+    const size_t n = h->post_coef1.size() * sizeof(float);
+    if (coef1) std::memcpy(coef1, h->post_coef1.data(), n);
+    if (coef2) std::memcpy(coef2, h->post_coef2.data(), n);
+    return CLD_OK;
+}
+
+int32_t cld_debug_recon_grid_cap(int32_t cap) { return recon_grid_cap(cap); }
+
+// what both calls check before anything is launched; *g2 receives the guidance as run_guidance is to see it: ONE evaluation of the
+// gradient, the optimiser fields (which these calls do not read) set to values that make its own update a no-op nobody looks at
+static int check_recon(cld_handle h, const char* fn, const cld_guidance* gd, const cld_recon* rc, int B, bool cfg, int iters,
+                       const void* ws, size_t ws_bytes, cld_guidance* g2) {
+    if (int r = check_f32(h, fn)) return r;
+    if (!h->finalized || !h->has_unet) return fail(h, CLD_ERR_STATE, std::string(fn) + ": the handle has no finalized U-Net weights (model.*)");
+    if (B < 1 || B > (1 << 19)) return fail(h, CLD_ERR_ARG, std::string(fn) + ": B out of range [1, 2^19]");
+    if (!gd || !rc) return fail(h, CLD_ERR_ARG, std::string(fn) + ": null guidance or recon");
+    if (!rc->params) return fail(h, CLD_ERR_ARG, std::string(fn) + ": recon->params is NULL (the flat U-Net buffer of cld_unet_param_info)");
+    if (gd->grad_steps > 1) return fail(h, CLD_ERR_ARG, std::string(fn) + ": grad_steps > 1 cannot run in this mode (upstream's second backward() goes through a freed graph)");
+    if (gd->apply_output) return fail(h, CLD_ERR_ARG, std::string(fn) + ": apply_output is not part of this mode");
+    if (gd->no_intermediate) return fail(h, CLD_ERR_ARG, std::string(fn) + ": no_intermediate leaves nothing to guide");
+    if (!ws || ws_bytes < cld_recon_workspace_bytes(h, B, cfg)) return fail(h, CLD_ERR_WORKSPACE, std::string(fn) + ": workspace too small (cld_recon_workspace_bytes)");
+    if (misaligned({ws, rc->params})) return fail(h, CLD_ERR_ARG, std::string(fn) + ": workspace and params must be 16-byte aligned");
+    *g2 = *gd;
+    g2->lr = 1.f; g2->perturb_th = -1.f; g2->optimizer = CLD_GUIDE_SGD; g2->grad_steps = 1; g2->final_grad_steps = 0; g2->guide_clean = 0;
+    return check_guidance(h, fn, g2, B, iters);
+}
+
+// One guided iteration (t = i > 0) on the latent in r.xt (both halves with CFG); leaves x_{i-1} there.
+static int recon_iteration(cld_handle h, const Ws& w, const ReconWs& r, bool cfg, int B, int i, const float* z, uint64_t seed,
+                           unsigned long long salt, float guidance_w, const cld_guidance* g2, const cld_recon* rc, float* x_next,
+                           float* x0_hat, float* grad_xt, float* x0_guided, float* mean, hipStream_t s) {
+    const int bn = cfg ? 2 * B : B;
+    const size_t half = (size_t)B * T * D;
+    const long rows = (long)B * T;
+    const float sigma = std::exp(0.5f * h->plvc[i]);
+    const float rca = h->sqrt_recip_acp[i], rm1 = h->sqrt_recipm1_acp[i];
+    HIPCK(h, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(r.tidx), i, (size_t)bn, s));
+    HIPCK(h, train_forward(rc->params, r.xt, r.cond2, r.tidx, r.eps, r.tape, bn, r.tws, s));
+    ReconHeadArgs ha{};
+    ha.eps_c = r.eps; ha.eps_u = cfg ? r.eps + half : nullptr; ha.x_t = r.xt; ha.x0_hat = r.x0;
+    ha.cfg_w = guidance_w; ha.rc = rca; ha.rm1 = rm1; ha.rows = rows;
+    HIPCK(h, launch_recon_head(ha, s));
+    // g0 = dL/dx0_hat: the mean-guided step's machinery on x0_hat, asked for its gradient only
+    if (int rcg = run_guidance(h, w, g2, B, true, sigma, 0.f, r.x0, r.cond2, nullptr, seed, salt, nullptr, nullptr, nullptr, r.g0, s)) return rcg;
+    ReconSeedArgs sa{};
+    sa.g0 = r.g0; sa.d_eps_c = r.deps; sa.d_eps_u = cfg ? r.deps + half : nullptr; sa.rows = rows;
+    sa.cc = cfg ? -(rm1 * (1.0f + guidance_w)) : -rm1; sa.cu = rm1 * guidance_w;
+    HIPCK(h, launch_recon_seed(sa, s));
+    HIPCK(h, train_backward(rc->params, r.xt, r.tape, r.deps, nullptr, r.dx, nullptr, 0, bn, r.tws, s));
+    ReconUpdateArgs ua{};
+    ua.g0 = r.g0; ua.dx_c = r.dx; ua.dx_u = cfg ? r.dx + half : nullptr; ua.x0_hat = r.x0; ua.x_t = r.xt; ua.z = z;
+    ua.x_out = r.xt; ua.x_out2 = cfg ? r.xt + half : nullptr; ua.x_next = x_next; ua.grad_xt = grad_xt; ua.x0_guided = x0_guided; ua.mean = mean;
+    const float lr_t = rc->lr > 0.f ? rc->lr : sigma;
+    ua.rc = rca; ua.slr = rc->descend ? -lr_t : lr_t;
+    if (rc->perturb_th < 0.f) ua.th = -1.f;
+    else if (rc->perturb_th == 0.f) ua.th = sigma;
+    else {      // diffuser.py:888-891, in double and rounded once
+        const double sc = 2.0 / (1.0 + std::exp(-10.0 * (double)i / (double)h->cfg.n_timesteps)) - 1.0;
+        ua.th = (float)(sc * (4.0 - (double)rc->perturb_th) + (double)rc->perturb_th);
+    }
+    ua.c1 = h->post_coef1[i]; ua.c2 = h->post_coef2[i]; ua.sigma = sigma; ua.seed = seed; ua.salt = salt; ua.rows = rows;
+    HIPCK(h, launch_recon_update(ua, s));
+    if (x0_hat) HIPCK(h, hipMemcpyAsync(x0_hat, r.x0, half * sizeof(float), hipMemcpyDeviceToDevice, s));
+    return CLD_OK;
+}
+
+// the rows the taped passes read besides the latent, and what the unguided t = 0 iteration needs in the sampler workspace
+static int recon_prepare(cld_handle h, const Ws& w, const ReconWs& r, bool cfg, int B, const float* x, const float* cond, const float* non_cond,
+                         hipStream_t s) {
+    const int bp = pad16(B);
+    const size_t half = (size_t)B * T * D;
+    HIPCK(h, hipMemcpyAsync(r.xt, x, half * sizeof(float), hipMemcpyDeviceToDevice, s));
+    HIPCK(h, hipMemcpyAsync(r.cond2, cond, (size_t)B * 256 * sizeof(float), hipMemcpyDeviceToDevice, s));
+    HIPCK(h, launch_cond_bias(cond, h->wc, h->cbias_b, w.cb, B, bp, NCB, s));
+    if (cfg) {
+        HIPCK(h, hipMemcpyAsync(r.xt + half, x, half * sizeof(float), hipMemcpyDeviceToDevice, s));
+        HIPCK(h, hipMemcpyAsync(r.cond2 + (size_t)B * 256, non_cond, (size_t)B * 256 * sizeof(float), hipMemcpyDeviceToDevice, s));
+        HIPCK(h, launch_cond_bias(non_cond, h->wc, h->cbias_b, w.cb + (size_t)bp * NCB, B, bp, NCB, s));
+    }
+    return CLD_OK;
+}
+
+// t = 0: the sampler's own unguided iteration on the latent in r.xt; leaves x_0 in w.xw and its mean in w.meanb
+static int recon_last(cld_handle h, const Ws& w, const ReconWs& r, bool cfg, int B, const float* z, uint64_t seed, unsigned long long salt,
+                      const float* cond, float guidance_w, hipStream_t s) {
+    const int bp = pad16(B);
+    HIPCK(h, launch_pack_latent(r.xt, w.xw, B, bp, s));
+    if (cfg) HIPCK(h, launch_pack_latent(r.xt, w.xw + (size_t)bp * T * D, B, bp, s));
+    return sample_iteration(h, w, cfg, B, bp, 0, z, seed, salt, cond, guidance_w, nullptr, nullptr, nullptr, false, s);
+}
+
+int cld_recon_step(cld_handle h, const float* x_t, const float* cond, const float* non_cond, float guidance_w, const cld_guidance* gd,
+                   const cld_recon* rc, int32_t t_idx, const float* z, float* x_next, float* x0_hat, float* grad_xt, float* x0_guided,
+                   float* mean, float* sigma_host, int32_t B, uint64_t seed, uint64_t salt, void* workspace, size_t workspace_bytes,
+                   void* stream) {
+    const bool cfg = non_cond != nullptr;
+    cld_guidance g2;
+    const int iters = salt < 65536 ? (int)salt + 1 : 65536;
+    int r0 = check_recon(h, "cld_recon_step", gd, rc, B, cfg, iters, workspace, workspace_bytes, &g2);
+    if (r0) return r0;
+    if (!x_t || !cond) return fail(h, CLD_ERR_ARG, "cld_recon_step: null pointer");
+    if (t_idx < 0 || t_idx >= h->cfg.n_timesteps) return fail(h, CLD_ERR_ARG, "cld_recon_step: timestep out of range");
+    if (sigma_host) *sigma_host = std::exp(0.5f * h->plvc[t_idx]);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int bp = pad16(B);
+    Ws w = carve(workspace, cfg ? 2 * bp : bp);
+    ReconWs r = recon_carve(h, workspace, B, cfg);
+    if ((r0 = recon_prepare(h, w, r, cfg, B, x_t, cond, non_cond, s)) != CLD_OK) return r0;
+    if (t_idx > 0) return recon_iteration(h, w, r, cfg, B, t_idx, z, seed, salt, guidance_w, &g2, rc, x_next, x0_hat, grad_xt, x0_guided, mean, s);
+    if ((r0 = recon_last(h, w, r, cfg, B, z, seed, salt, cond, guidance_w, s)) != CLD_OK) return r0;
+    if (x_next) HIPCK(h, launch_unpack(w.xw, x_next, B, s));
+    if (mean) HIPCK(h, launch_unpack(w.meanb, mean, B, s));
+    return CLD_OK;
+}
+
+int cld_sample_recon(cld_handle h, const float* x_T, const float* noise, const float* cond, const float* non_cond, float guidance_w,
+                     const cld_guidance* gd, const cld_recon* rc, int32_t steps, float* x0, float* x1, float* logp, int32_t B,
+                     uint64_t seed, void* workspace, size_t workspace_bytes, void* stream) {
+    const bool cfg = non_cond != nullptr;
+    cld_guidance g2;
+    int r0 = check_recon(h, "cld_sample_recon", gd, rc, B, cfg, steps > 0 ? steps : 1, workspace, workspace_bytes, &g2);
+    if (r0) return r0;
+    if (!x_T || !cond) return fail(h, CLD_ERR_ARG, "cld_sample_recon: null pointer");
+    if (steps != loop_steps(h))
+        return fail(h, CLD_ERR_ARG, "cld_sample_recon: steps must equal len(range(0, n_timesteps, stride)) = " + std::to_string(loop_steps(h)));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int bp = pad16(B);
+    Ws w = carve(workspace, cfg ? 2 * bp : bp);
+    ReconWs r = recon_carve(h, workspace, B, cfg);
+    if ((r0 = recon_prepare(h, w, r, cfg, B, x_T, cond, non_cond, s)) != CLD_OK) return r0;
+    for (int it = 0; it < steps; ++it) {
+        const int i = (steps - 1 - it) * h->stride;
+        const float* z = noise ? noise + (size_t)it * B * T * D : nullptr;
+        if (i > 0) {
+            r0 = recon_iteration(h, w, r, cfg, B, i, z, seed, (unsigned long long)it, guidance_w, &g2, rc, i == 1 ? x1 : nullptr, nullptr, nullptr,
+                                 nullptr, nullptr, s);
+            if (r0) return r0;
+        } else {
+            if ((r0 = recon_last(h, w, r, cfg, B, z, seed, (unsigned long long)it, cond, guidance_w, s)) != CLD_OK) return r0;
+            if (x0) HIPCK(h, launch_unpack(w.xw, x0, B, s));
+            if (logp) HIPCK(h, launch_logprob(w.xw, w.meanb, std::exp(0.5f * h->plvc[0]), logp, B, s));
+        }
+    }
     return CLD_OK;
 }
 

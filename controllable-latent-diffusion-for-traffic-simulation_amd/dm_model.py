@@ -157,7 +157,9 @@ class DmModel:
         """`class_free_guide_w` != 0 needs aux_info['non_cond_feat'] and follows the upstream CFG definition
         (src/tbsim/models/diffuser.py:766-789; kwarg name as injected by policies/wrappers.py:143-167).
         `guidance` = dict(target_speed [B,52], loss_scale [B] | None, lr, perturb_th, optimizer): sampling-time guidance
-        of every step's posterior mean (upstream diffuser.py:844-929; Engine._guidance); curr_states come from aux_info."""
+        of every step's posterior mean (upstream diffuser.py:844-929; Engine._guidance); curr_states come from aux_info.  A
+        `reconstruction` entry (Engine._recon: params, lr, perturb_th, descend) is passed through as it is and selects upstream's
+        guide_clean="video_diff" (include/cld_recon.h)."""
         batch_size = data_batch["history_positions"].size()[0]
         num_samp = int(cfg_get(algo_config, "num_samp", 1))
         BN = batch_size * num_samp

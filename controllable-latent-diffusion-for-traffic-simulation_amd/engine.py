@@ -85,6 +85,19 @@ def unet_param_table(lib=None, h=None):
     return _param_table(lib, h, "unet")
 
 
+def copy_into_flat(views: Mapping, sd: Mapping, device) -> None:
+    """Copy the tensors of `sd` into the views of a flat parameter buffer (`views`: name -> a view shaped as the table says); names
+    `sd` lacks are left as they are, a shape that disagrees is an error.  What `train._FlatParams.load_state_dict` and
+    `Engine.unet_flat_params` share."""
+    with torch.no_grad():
+        for k, p in views.items():
+            if k in sd:
+                v = torch.as_tensor(sd[k]).to(device=device, dtype=torch.float32)
+                if tuple(v.shape) != tuple(p.shape):
+                    raise CldError(f"load_state_dict: '{k}' expects shape {tuple(p.shape)}, got {tuple(v.shape)}")
+                p.copy_(v)
+
+
 def vae_param_table(lib=None, h=None):
     """cld_vae_param_info for all 26 LSTMVAE tensors, as unet_param_table."""
     return _param_table(lib, h, "vae")
@@ -128,9 +141,11 @@ class Engine:
             rc = self.lib.cld_create(C.byref(cfg), C.byref(self._h))
         if rc != 0:
             raise CldError(f"cld_create failed ({rc})")
-        self._ws = self._ctx_ws = self._tws = self._vws = self._rws = None      # grow-only device scratch (_scratch): sampling, ContextEncoder,
-                                                                                # U-Net training, VAE training, sort / Wasserstein
+        self._ws = self._ctx_ws = self._tws = self._vws = self._rws = self._recon_ws = None      # grow-only device scratch (_scratch): sampling, ContextEncoder,
+                                                                                # U-Net training, VAE training, sort / Wasserstein,
+                                                                                # reconstruction guidance
         self._nc_map_feat = {}
+        self._unet_sd = {}
         self._finalized = False
         self.precision = {v: k for k, v in _lib.PRECISIONS.items()}[int(self.lib.cld_get_precision(self._h))]
         n = self.n_timesteps
@@ -242,6 +257,9 @@ class Engine:
         if self._finalized:
             raise CldError("weights already finalized")
         for k, v in sd.items():
+            name = k[3:] if k.startswith("dm.") else k
+            if name.startswith("model."):      # references, not copies: what unet_flat_params() builds the training-layout buffer from
+                self._unet_sd[name] = v
             a = v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
             a = np.ascontiguousarray(a, dtype=np.float32)
             rc = self.lib.cld_load_weight(self._h, k.encode(), a.ctypes.data, a.size)
@@ -1013,7 +1031,9 @@ class Engine:
         """Full ancestral loop.  With `non_cond` [B,256] and guidance_w != 0: classifier-free guidance
         (eps = (1+w) eps_cond - w eps_uncond, upstream diffuser.py:787), both passes as one 2B batch per step.
         With `guidance` (see `_guidance`): the posterior mean of every step t > 0 takes one optimiser step on the
-        target-speed loss through decoder + roll-out before the noise is added (upstream diffuser.py:844-929)."""
+        target-speed loss through decoder + roll-out before the noise is added (upstream diffuser.py:844-929).
+        With guidance["reconstruction"] (see `_recon`): upstream's guide_clean="video_diff" instead -- the gradient is taken with respect
+        to the noisy latent, through the denoiser (cld_sample_recon, include/cld_recon.h)."""
         x_T = self._f32(x_T)
         B = x_T.shape[0]
         x_T = self._f32(x_T, (B, T, D)); cond = self._f32(cond, (B, COND))
@@ -1025,7 +1045,15 @@ class Engine:
         logp = torch.empty(B, dtype=torch.float32, device=self.device) if want_logp else None
         cfg = non_cond is not None and guidance_w != 0.0
         with torch.cuda.device(self.device), self._goal_term(guidance, B), self._social_term(guidance, B), self._pair_term(guidance, B), self._lane_term(guidance, B), self._map_source_term((guidance or {}).get("map_collision"), B):
-            if guidance is not None:
+            if guidance is not None and guidance.get("reconstruction") is not None:
+                cg, keep = self._guidance(guidance, B)
+                rc, rkeep = self._recon(guidance["reconstruction"])
+                non_cond = self._f32(non_cond, (B, COND)) if cfg else None
+                ws, wsn = self._recon_workspace(B, cfg)
+                self._check(self.lib.cld_sample_recon(self._h, _ptr(x_T), _ptr(noise), _ptr(cond), _ptr(non_cond),
+                                                      C.c_float(guidance_w), C.byref(cg), C.byref(rc), n, _ptr(x0), _ptr(x1), _ptr(logp),
+                                                      B, C.c_uint64(seed), ws, wsn, self._stream()), "cld_sample_recon")
+            elif guidance is not None:
                 cg, keep = self._guidance(guidance, B)
                 non_cond = self._f32(non_cond, (B, COND)) if cfg else None
                 ws, wsn = self._workspace(2 * ((B + 15) // 16 * 16) if cfg else B)
@@ -1073,6 +1101,76 @@ class Engine:
             out["mean_guided"] = mg
             if want_grad:
                 out["grad"] = gr
+        return out
+
+    # ------------------------------------------------------------------ reconstruction guidance (include/cld_recon.h)
+    def unet_flat_params(self, state_dict: Optional[Mapping] = None) -> torch.Tensor:
+        """The U-Net weights of `state_dict` ("model.*" keys, optional "dm." prefix) as ONE flat fp32 device buffer in the layout
+        of `unet_param_table`: what the taped forward and the backward of reconstruction guidance read.  Every tensor of the table
+        must be present.  None: the tensors `load_state_dict` was given (the engine keeps references to them, not copies: they must
+        not have been changed since)."""
+        table, nflat = self.unet_param_table()
+        sd = {(k[3:] if k.startswith("dm.") else k): v for k, v in (self._unet_sd if state_dict is None else state_dict).items()}
+        missing = [name for name, *_ in table if name not in sd]
+        if missing:
+            raise CldError(f"unet_flat_params: missing {missing[:4]}")
+        flat = torch.zeros(nflat, dtype=torch.float32, device=self.device)
+        copy_into_flat({name: flat[off:off + n].view(shape) for name, off, n, shape in table}, sd, self.device)
+        return flat
+
+    def posterior_mean_coefs(self):
+        """(posterior_mean_coef1, posterior_mean_coef2) of dm_model.py:50-53 as the handle holds them, float32 [n_timesteps] each."""
+        c1, c2 = (np.empty(self.n_timesteps, np.float32) for _ in range(2))
+        self._check(self.lib.cld_recon_get_posterior(self._h, c1.ctypes.data, c2.ctypes.data), "cld_recon_get_posterior")
+        return c1, c2
+
+    def _recon(self, r: Mapping):
+        """dict(params: the flat buffer of `unet_flat_params` for the weights this engine was finalized with, lr: None = sigma_t,
+        perturb_th: None = clip to sigma_t (upstream's `perturb_th is None`) | a number > 0 = upstream's schedule towards it | "none" =
+        no clip, descend: False = upstream's sign AS WRITTEN, which ascends the loss | True = the evident intent)
+        -> (CldRecon, tensors kept alive)."""
+        params = r.get("params")
+        if params is not None:
+            if not isinstance(params, torch.Tensor) or params.dtype != torch.float32 or not params.is_cuda or not params.is_contiguous():
+                raise CldError("reconstruction: params must be a contiguous float32 tensor on the engine's device (Engine.unet_flat_params)")
+            if params.numel() != self.unet_param_table()[1]:
+                raise CldError(f"reconstruction: params has {params.numel()} floats, the table asks for {self.unet_param_table()[1]}")
+        th = r.get("perturb_th")
+        if th is not None and th != "none" and not float(th) > 0.0:
+            raise CldError("reconstruction: perturb_th is None (sigma_t), a number > 0, or \"none\"")
+        rc = _lib.CldRecon(None if params is None else params.data_ptr(), float(r["lr"]) if r.get("lr") else 0.0, 0.0 if th is None else (-1.0 if th == "none" else float(th)),
+                           1 if r.get("descend") else 0)
+        return rc, (params,)
+
+    def _recon_workspace(self, B: int, cfg: bool):
+        return self._scratch("_recon_ws", int(self.lib.cld_recon_workspace_bytes(self._h, B, int(cfg))))
+
+    def recon_step(self, x_t, cond, t_idx: int, guidance: Mapping, z=None, non_cond=None, guidance_w: float = 0.0, seed: int = 0,
+                   salt: int = 0):
+        """One iteration of `sample(..., guidance=dict(..., reconstruction=...))` at timestep t_idx on a given x_t (cld_recon_step;
+        upstream p_sample with guide_clean="video_diff", diffuser.py:844-929) -> dict(x_next, mean, sigma, and at t_idx > 0 x0_hat,
+        grad_xt = dL/dx_t, x0_guided).  z None: the step's noise is drawn on the device for (seed, salt)."""
+        x_t = self._f32(x_t)
+        B = x_t.shape[0]
+        x_t = self._f32(x_t, (B, T, D)); cond = self._f32(cond, (B, COND))
+        z = None if z is None else self._f32(z, (B, T, D))
+        cfg = non_cond is not None and guidance_w != 0.0
+        non_cond = self._f32(non_cond, (B, COND)) if cfg else None
+        cg, keep = self._guidance(guidance, B)
+        rc, rkeep = self._recon(guidance.get("reconstruction") or {})
+        guided = t_idx > 0
+        xn, mean = torch.empty_like(x_t), torch.empty_like(x_t)
+        x0h, gx, x0g = ((torch.empty_like(x_t) for _ in range(3)) if guided else (None, None, None))
+        ws, wsn = self._recon_workspace(B, cfg)
+        sigma = C.c_float()
+        with torch.cuda.device(self.device), self._goal_term(guidance, B), self._social_term(guidance, B), self._pair_term(guidance, B), self._lane_term(guidance, B), self._map_source_term((guidance or {}).get("map_collision"), B):
+            self._check(self.lib.cld_recon_step(self._h, _ptr(x_t), _ptr(cond), _ptr(non_cond), C.c_float(guidance_w), C.byref(cg),
+                                                C.byref(rc), int(t_idx), _ptr(z), _ptr(xn), _ptr(x0h), _ptr(gx), _ptr(x0g), _ptr(mean),
+                                                C.byref(sigma), B, C.c_uint64(seed), C.c_uint64(salt), ws, wsn, self._stream()),
+                        "cld_recon_step")
+        out = {"x_next": xn, "mean": mean, "sigma": float(sigma.value)}
+        if guided:
+            out.update(x0_hat=x0h, grad_xt=gx, x0_guided=x0g)
         return out
 
     # ------------------------------------------------------------------ training (exact fp32; cld_unet_train_forward / cld_unet_backward)

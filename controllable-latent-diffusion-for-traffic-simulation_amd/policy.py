@@ -239,8 +239,23 @@ class CldPolicy:
         self.goal_global_t = None
         self.goal_reached_by = "any"
         self.social_iter = 0                          # evaluation index of the next plan's first loop iteration (social-group draws)
+        self._reconstruction = None                   # enable_reconstruction_guidance: what guide_clean="video_diff" runs with
 
     def eval(self):
+        return self
+
+    def enable_reconstruction_guidance(self, descend: bool = False, lr: Optional[float] = None, perturb_th=None, weights: Optional[Mapping] = None):
+        """Prepare `get_action(guide_clean="video_diff")`: upstream's reconstruction guidance (DiffuserModel.p_sample,
+        diffuser.py:844-929, with perturb_video_diffusion, guidance_loss.py:2284-2330) -- the mode both shipped checkpoints configure.
+        The mode differentiates the guidance loss through the DENOISER, so it holds a second copy of the U-Net weights on the
+        device, in the training layout (17 MB), and per plan a tape of `cld_unet_tape_bytes(h, 1)` per row (twice that with
+        classifier-free guidance); a policy does not allocate those unasked, hence this call.  `weights`: the U-Net state_dict the
+        DmModel was loaded with (None: the tensors it was given, which must be unchanged).
+        descend=False reproduces upstream AS WRITTEN: x0_hat + lr * grad (guidance_loss.py:2319-2324), which with upstream's positive
+        loss totals ASCENDS the loss; descend=True is the evident intent.  lr None = sigma_t; perturb_th None = clip to sigma_t, a
+        number > 0 = upstream's schedule towards it (diffuser.py:888-891), "none" = no clip.  The optimiser settings of
+        `set_guidance` (lr / optimizer / perturb_th) are not read in this mode (scene_edit_config.py:74)."""
+        self._reconstruction = dict(params=self.dm.engine.unet_flat_params(weights), lr=lr, perturb_th=perturb_th, descend=bool(descend))
         return self
 
     def set_guidance(self, guidance_config_list, scene_index, **opt):
@@ -413,15 +428,19 @@ class CldPolicy:
         info['guide_losses'], and the executed sample is the one `choose_action_from_guidance` picks (algos.py:2057-2064);
         `guide_as_filter_only`: sample without guidance and only filter (algos.py:1815); `guide_with_gt`: the sample closest to
         obs_dict['target_positions'] (algos.py:2055-2056); `guide_clean=True`: the guidance steps act on the model's clean
-        prediction (diffuser.py:866-873; its "video_diff" variant, which re-derives the posterior, is not built and raises).  A
+        prediction (diffuser.py:866-873); `guide_clean="video_diff"`: reconstruction guidance, after enable_reconstruction_guidance().  A
         collision config (`agent_collision`, guidance_loss.py:442-630) is filed under guide_losses and makes the sample choice
         scene-level, as upstream's SCENE_LEVEL_LOSSES do.  A goal config (`global_target_pos`, `global_target_pos_at_time`,
         guidance_loss.py:930-1135) reads obs_dict['agent_from_world'] and / or ['world_from_agent'] [B,3,3] (one is computed from the
         other; ValueError without both) and, with a target_tolerance, obs_dict['agent_hist'] [B,Th,>=2]; `step_index` is its global_t
         (algos.py:2048); the arrival flags persist on the policy (`goal_reached`) and come back as info['goal_reached'].
         Not built: `plan` -- it raises instead of being ignored."""
-        if guide_clean not in (False, True, 0, 1, None):
-            raise NotImplementedError(f"guide_clean={guide_clean!r}: only the boolean form is built (diffuser.py:866-873)")
+        video_diff = isinstance(guide_clean, str) and guide_clean == "video_diff"
+        if video_diff and self._reconstruction is None:
+            raise NotImplementedError("guide_clean='video_diff' needs CldPolicy.enable_reconstruction_guidance() first: the mode keeps a "
+                                      "second copy of the U-Net weights and a tape per row, which a policy does not allocate unasked")
+        if not video_diff and guide_clean not in (False, True, 0, 1, None):
+            raise NotImplementedError(f"guide_clean={guide_clean!r}: the boolean form and \"video_diff\" are built (diffuser.py:866-873)")
         if plan is not None:
             raise NotImplementedError("plan conditioning is not part of the CLD sampler")
         if kwargs:
@@ -438,9 +457,12 @@ class CldPolicy:
             aux["non_cond_feat"] = eng.non_cond_feat(cs)            # upstream builds it itself (diffuser.py:390-411,459-471); raises without the ContextEncoder weights
         B, N = cond.shape[0], int(num_action_samples)
         g = guidance if guidance is not None else self._guidance
-        if g is not None and guide_clean:
+        set_by_config = g is self._guidance
+        if g is not None and video_diff:      # without guidance the mode is upstream's no-op: the plain chain
+            g = dict(g, reconstruction=self._reconstruction)
+        elif g is not None and guide_clean:
             g = dict(g, guide_clean=True)
-        from_cfg = g is self._guidance and self._guidance_cfg is not None
+        from_cfg = (g is self._guidance or (video_diff and set_by_config)) and self._guidance_cfg is not None
         if guidance is None and self._follow_observation:           # the collision terms of set_guidance follow this observation
             g = refresh_lane_term(refresh_pair_term(refresh_social_term(refresh_collision_terms(g, obs_dict), obs_dict), obs_dict), obs_dict)
         if g is not None and g.get("social_group") is not None and guidance is None:

@@ -20,7 +20,7 @@ import torch.nn.functional as F
 
 from ._lib import CldError
 from .dm_model import DmModel
-from .engine import Engine, unet_param_table
+from .engine import Engine, copy_into_flat, unet_param_table
 from .vae_model import VaeModel
 
 
@@ -88,13 +88,7 @@ class _FlatParams:
         unknown = [k for k in sd if k not in self._params and k.startswith(self._KEYS)]
         if strict and (missing or unknown):
             raise CldError(f"load_state_dict: missing {missing[:4]}, unknown {unknown[:4]}")
-        with torch.no_grad():
-            for k, p in self._params.items():
-                if k in sd:
-                    v = torch.as_tensor(sd[k]).to(device=self.device, dtype=torch.float32)
-                    if tuple(v.shape) != tuple(p.shape):
-                        raise CldError(f"load_state_dict: '{k}' expects shape {tuple(p.shape)}, got {tuple(v.shape)}")
-                    p.copy_(v)
+        copy_into_flat(self._params, sd, self.device)
         return self
 
     def zero_grad(self, set_to_none: bool = True):

@@ -223,8 +223,8 @@ typedef struct cld_guidance {
     int32_t final_grad_steps;
     /* guide_clean != 0: upstream's `guide_clean=True` (diffuser.py:866-873): the optimiser steps act on the model's CLEAN
      * prediction x0_hat = sqrt(1 / acp_t) x_t - sqrt(1 / acp_t - 1) eps instead of on the posterior mean, and x_{t-1} is that
-     * guided x0_hat + sigma_t z (upstream does not re-derive the posterior from it unless guide_clean == "video_diff", which is
-     * not built).  PARITY UNPINNED beyond the oracle's restatement: no shipped config turns it on. */
+     * guided x0_hat + sigma_t z (upstream does not re-derive the posterior from it unless guide_clean == "video_diff": that mode,
+     * reconstruction guidance, has calls of its own in include/cld_recon.h and does not read this field).  PARITY UNPINNED beyond the oracle's restatement: no shipped config turns it on. */
     int32_t guide_clean;
     /* AgentCollisionLoss (guidance_loss.py:442-630) as a term of the guidance loss: every guided step decodes the current
      * iterate, evaluates the loss and its gradient w.r.t. the decoded plans on the device (cld_agent_collision) and feeds it
