@@ -755,6 +755,25 @@ const std::vector<float>* getw(cld_handle h, const std::string& k) {
     return it == h->w.end() ? nullptr : &it->second;
 }
 
+// what is behind every cld_set_*_term and cld_set_map_source: the handle keeps a COPY of *term for the guided calls that follow; NULL clears it
+template <class Term>
+int set_term(cld_handle h, const Term* term, Term cld_handle_s::*slot, bool cld_handle_s::*has) {
+    if (!h) return CLD_ERR_ARG;
+    h->*has = term != nullptr;
+    h->*slot = term ? *term : Term{};
+    return CLD_OK;
+}
+
+// The sampler's inputs into its workspace: the latent `x` packed into w.xw, the conditioning bias rows of `cond` into w.cb; with CFG
+// once more behind them, rows [bp, 2 bp): the same latent, the bias rows of `non_cond`.  x / cond NULL: that part is there already.
+int load_inputs(cld_handle h, const Ws& w, int B, int bp, const float* x, const float* cond, const float* non_cond, bool cfg, hipStream_t s) {
+    for (int half = 0; half < (cfg ? 2 : 1); ++half) {
+        if (x) HIPCK(h, launch_pack_latent(x, w.xw + (size_t)half * bp * T * D, B, bp, s));
+        if (cond) HIPCK(h, launch_cond_bias(half ? non_cond : cond, h->wc, h->cbias_b, w.cb + (size_t)half * bp * NCB, B, bp, NCB, s));
+    }
+    return CLD_OK;
+}
+
 }  // namespace
 
 // =============================================================================================
@@ -1369,8 +1388,7 @@ int cld_unet_forward(cld_handle h, const float* x, const float* cond, int32_t t_
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int bp = pad16(B);
     Ws w = carve(workspace, bp);
-    HIPCK(h, launch_pack_latent(x, w.xw, B, bp, s));
-    HIPCK(h, launch_cond_bias(cond, h->wc, h->cbias_b, w.cb, B, bp, NCB, s));
+    if ((rc = load_inputs(h, w, B, bp, x, cond, nullptr, false, s)) != CLD_OK) return rc;
     HIPCK(h, run_unet(h, w, w.xw, t_idx, bp, s));
     HeadArgs a{};
     head_source(h, w, a); a.w = h->head_w; a.b = h->head_b; a.x = w.xw; a.eps_out = eps; a.B = B; a.b_pad = bp;
@@ -1386,8 +1404,7 @@ int cld_unet_forward_t(cld_handle h, const float* x, const float* cond, const in
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int bp = pad16(B);
     Ws w = carve(workspace, bp);
-    HIPCK(h, launch_pack_latent(x, w.xw, B, bp, s));
-    HIPCK(h, launch_cond_bias(cond, h->wc, h->cbias_b, w.cb, B, bp, NCB, s));
+    if ((rc = load_inputs(h, w, B, bp, x, cond, nullptr, false, s)) != CLD_OK) return rc;
     HIPCK(h, launch_add_time_bias(w.cb, h->tb, t_idx, h->cfg.n_timesteps, B, NCB, s));
     HIPCK(h, run_unet(h, w, w.xw, -1, bp, s));
     HeadArgs a{};
@@ -1457,8 +1474,7 @@ int cld_ddpm_step(cld_handle h, const float* x, const float* cond, int32_t t_idx
     Ws w = carve(workspace, bp);
     const float sigma = std::exp(0.5f * h->plvc[t_idx]);
     if (sigma_host) *sigma_host = sigma;
-    HIPCK(h, launch_pack_latent(x, w.xw, B, bp, s));
-    HIPCK(h, launch_cond_bias(cond, h->wc, h->cbias_b, w.cb, B, bp, NCB, s));
+    if ((rc = load_inputs(h, w, B, bp, x, cond, nullptr, false, s)) != CLD_OK) return rc;
     HIPCK(h, run_unet(h, w, w.xw, t_idx, bp, s));
     HeadArgs a{};
     head_source(h, w, a); a.w = h->head_w; a.b = h->head_b; a.x = w.xw; a.z = z; a.B = B; a.b_pad = bp;
@@ -1478,6 +1494,14 @@ static int check_collision(cld_handle h, const char* fn, const cld_collision* c,
     // 192: the largest scene whose poses fit launch_agent_collision's 160-KiB LDS request (163,664 B; 193 agents would need 164,512)
     if (c->max_scene_agents < 1 || c->max_scene_agents > 192) return fail(h, CLD_ERR_ARG, std::string(fn) + ": collision term: scenes of 1..192 agents");
     return CLD_OK;
+}
+static CollisionArgs collision_args(const cld_collision* c, const float* traj, const float* grad_in, float* loss, float* grad, int B) {
+    CollisionArgs a{};
+    a.traj = traj; a.extent = c->extent; a.world_from_agent = c->world_from_agent; a.curr_speed = c->curr_speed;
+    a.scene_start = c->scene_start; a.scene_weight = c->scene_weight; a.guided = c->guided; a.excluded = c->excluded; a.max_scene_agents = c->max_scene_agents; a.grad_in = grad_in;
+    a.loss = loss; a.grad = grad; a.B_agents = B / c->num_samp; a.num_scenes = c->num_scenes; a.num_samp = c->num_samp;
+    a.num_disks = c->num_disks; a.buffer_dist = c->buffer_dist; a.decay_rate = c->decay_rate; a.moving_speed_th = c->moving_speed_th;
+    return a;
 }
 
 static int check_map_collision(cld_handle h, const char* fn, const cld_map_collision* c, int B) {
@@ -1596,36 +1620,29 @@ static LaneArgs lane_args(const cld_lane_term* t, const float* traj, float* valu
     return a;
 }
 
+// The plan-space terms -- functions of the decoded plans of the current iterate, chained through the gradient buffer in THIS order
+// (run_guidance) -- that a guided call on (handle, guidance) evaluates.  A new term: a bit here, its *_args() builder and check_*()
+// above, a line in check_guidance and a block in run_guidance's chain.
+enum : unsigned { TERM_COLLISION = 1, TERM_MAP = 2, TERM_GOAL = 4, TERM_SOCIAL = 8, TERM_PAIR = 16, TERM_LANE = 32 };
+static unsigned plan_terms(cld_handle h, const cld_guidance* gd) {
+    return (gd->collision ? TERM_COLLISION : 0u) | (gd->map_collision ? TERM_MAP : 0u) | (h->has_goal ? TERM_GOAL : 0u) |
+           (h->has_social ? TERM_SOCIAL : 0u) | (h->has_pair ? TERM_PAIR : 0u) | (h->has_lane ? TERM_LANE : 0u);
+}
+
 static int check_guidance(cld_handle h, const char* fn, const cld_guidance* gd, int B, int iters = 1) {
     if (!h->has_decoder) return fail(h, CLD_ERR_STATE, std::string(fn) + ": guidance needs the decoder weights");
-    if (!gd->curr_states || (!gd->target_speed && !gd->speed_limit_scale && !gd->acc_limit_scale && !gd->target_pos_scale && !gd->ext_grad && !gd->collision && !gd->map_collision && !h->has_goal && !h->has_social && !h->has_pair && !h->has_lane))
+    const unsigned terms = plan_terms(h, gd);
+    if (!gd->curr_states || (!terms && !gd->target_speed && !gd->speed_limit_scale && !gd->acc_limit_scale && !gd->target_pos_scale && !gd->ext_grad))
         return fail(h, CLD_ERR_ARG, std::string(fn) + ": guidance needs curr_states and at least one loss term");
-    if (gd->collision) {
-        const int rcc = check_collision(h, fn, gd->collision, B);
-        if (rcc) return rcc;
-    }
-    if (gd->map_collision) {
-        const int rcc = check_map_collision(h, fn, gd->map_collision, B);
-        if (rcc) return rcc;
-    }
-    if (h->has_goal) {
-        const int rcc = check_goal(h, fn, &h->goal, B);
-        if (rcc) return rcc;
-    }
-    if (gd->grad_steps < 0 || gd->final_grad_steps < 0 || gd->grad_steps > 64 || gd->final_grad_steps > 64)
+    int rc;
+    if ((terms & TERM_COLLISION) && (rc = check_collision(h, fn, gd->collision, B))) return rc;
+    if ((terms & TERM_MAP) && (rc = check_map_collision(h, fn, gd->map_collision, B))) return rc;
+    if ((terms & TERM_GOAL) && (rc = check_goal(h, fn, &h->goal, B))) return rc;
+    if (gd->grad_steps < 0 || gd->final_grad_steps < 0 || gd->grad_steps > 64 || gd->final_grad_steps > 64)      // (what the social term's draws are checked against)
         return fail(h, CLD_ERR_ARG, std::string(fn) + ": grad_steps out of range (0..64)");
-    if (h->has_social) {
-        const int rcc = check_social(h, fn, &h->social, B, iters, std::max(gd->grad_steps, gd->final_grad_steps));
-        if (rcc) return rcc;
-    }
-    if (h->has_pair) {
-        const int rcc = check_pair(h, fn, &h->pair, B);
-        if (rcc) return rcc;
-    }
-    if (h->has_lane) {
-        const int rcc = check_lane(h, fn, &h->lane, B);
-        if (rcc) return rcc;
-    }
+    if ((terms & TERM_SOCIAL) && (rc = check_social(h, fn, &h->social, B, iters, std::max(gd->grad_steps, gd->final_grad_steps)))) return rc;
+    if ((terms & TERM_PAIR) && (rc = check_pair(h, fn, &h->pair, B))) return rc;
+    if ((terms & TERM_LANE) && (rc = check_lane(h, fn, &h->lane, B))) return rc;
     if (gd->optimizer != CLD_GUIDE_ADAM && gd->optimizer != CLD_GUIDE_SGD) return fail(h, CLD_ERR_ARG, std::string(fn) + ": unknown optimizer");
     if (gd->apply_output && gd->final_optimizer != CLD_GUIDE_ADAM && gd->final_optimizer != CLD_GUIDE_SGD)
         return fail(h, CLD_ERR_ARG, std::string(fn) + ": unknown optimizer for the output step");
@@ -1633,20 +1650,27 @@ static int check_guidance(cld_handle h, const char* fn, const cld_guidance* gd, 
     return CLD_OK;
 }
 
+// the terms the guidance kernel evaluates itself: target speed, speed and acceleration limits, waypoint
+static GuideArgs builtin_terms(const cld_guidance* gd) {
+    GuideArgs g{};
+    g.target_speed = gd->target_speed; g.loss_scale = gd->loss_scale;
+    g.speed_limit_scale = gd->speed_limit_scale; g.acc_limit_scale = gd->acc_limit_scale;
+    g.speed_limit = gd->speed_limit; g.acc_limit = gd->acc_limit;
+    g.target_pos = gd->target_pos; g.target_time = gd->target_time; g.target_pos_scale = gd->target_pos_scale;
+    return g;
+}
+
 // The guidance step(s) of one denoising iteration on the posterior mean `mean0` (upstream perturb(), guidance_loss.py:2221-2282):
 // grad_steps optimiser steps, each one guidance-kernel launch (decoder forward + roll-out + loss gradients + BPTT + update) on the
-// current iterate; with a collision term each step first decodes the iterate and runs the AgentCollisionLoss kernel, whose
-// gradient w.r.t. the plans enters the guidance kernel as ext_grad.  The last step adds sigma z and writes x_out (/ x_out2).
+// current iterate; with plan-space terms (plan_terms) each step first decodes the iterate and runs their loss kernels in the chain's
+// order, whose summed gradient w.r.t. the plans enters the guidance kernel as ext_grad.  The last step adds sigma z and writes x_out (/ x_out2).
 // `intermediate`: a t > 0 step (lr / perturb_th / optimizer / grad_steps) or the output step (final_*).
 static int run_guidance(cld_handle h, const Ws& w, const cld_guidance* gd, int B, bool intermediate, float sigma_t, float sigma_noise,
                         const float* mean0, const float* cond, const float* z, uint64_t seed, unsigned long long salt,
                         float* mean_out, float* x_out, float* x_out2, float* grad_out, hipStream_t s) {
-    GuideArgs g{};
-    g.cond = cond; g.curr_states = gd->curr_states; g.target_speed = gd->target_speed; g.loss_scale = gd->loss_scale;
-    g.speed_limit_scale = gd->speed_limit_scale; g.acc_limit_scale = gd->acc_limit_scale;
-    g.speed_limit = gd->speed_limit; g.acc_limit = gd->acc_limit;
-    g.target_pos = gd->target_pos; g.target_time = gd->target_time; g.target_pos_scale = gd->target_pos_scale;
-    g.ext_grad = gd->ext_grad;
+    const unsigned terms = plan_terms(h, gd);
+    GuideArgs g = builtin_terms(gd);
+    g.cond = cond; g.curr_states = gd->curr_states;
     // t = 0 (apply_guidance_output): the step's own optimiser settings, and no noise behind it (nonzero_mask, diffuser.py:929)
     const float lr_in = intermediate ? gd->lr : gd->final_lr, th_in = intermediate ? gd->perturb_th : gd->final_perturb_th;
     g.scratch = w.guide; g.lr = lr_in > 0.f ? lr_in : sigma_t; g.perturb_th = th_in > 0.f ? th_in : (th_in == 0.f ? sigma_t : -1.f);
@@ -1658,7 +1682,8 @@ static int run_guidance(cld_handle h, const Ws& w, const cld_guidance* gd, int B
         const bool last = k == steps;
         g.opt_step = k;
         g.mean = k == 1 ? mean0 : w.gcur;
-        if (gd->collision || gd->map_collision || h->has_goal || h->has_social || h->has_pair || h->has_lane) {    // the scene / map / goal / social / pair / lane terms are functions of the decoded plans of the current iterate
+        const float* gin = gd->ext_grad;                 // the gradient w.r.t. the plans so far: the caller's, then w.col_grad, to which every term adds its own
+        if (terms) {                                     // the plan-space terms are functions of the decoded plans of the current iterate
             if (B >= 256 && guide_forward_available(B, h->force_kernel[CLD_KERNEL_GUIDE]) && h->force_kernel[CLD_KERNEL_DECODE] == FORM_AUTO) {
                 // (from the batch size at which cld_decode itself would take its 16-agent MFMA form, ~0.3 ms; below that the
                 //  one-agent-per-workgroup decoder is the shorter chain: 64 agents 579 vs 616 us per collision-guided step)
@@ -1675,39 +1700,31 @@ static int run_guidance(cld_handle h, const Ws& w, const cld_guidance* gd, int B
                 HIPCK(h, launch_decode(h->dec, h->dyn, g.mean, cond, gd->curr_states, nullptr, w.col_traj, B, 1, s, h->force_kernel[CLD_KERNEL_DECODE]));
             }
         }
-        if (gd->collision) {
-            const cld_collision* c = gd->collision;
-            CollisionArgs ca{};
-            ca.traj = w.col_traj; ca.extent = c->extent; ca.world_from_agent = c->world_from_agent; ca.curr_speed = c->curr_speed;
-            ca.scene_start = c->scene_start; ca.scene_weight = c->scene_weight; ca.guided = c->guided; ca.excluded = c->excluded; ca.max_scene_agents = c->max_scene_agents; ca.grad_in = gd->ext_grad;
-            ca.grad = w.col_grad; ca.B_agents = B / c->num_samp; ca.num_scenes = c->num_scenes; ca.num_samp = c->num_samp;
-            ca.num_disks = c->num_disks; ca.buffer_dist = c->buffer_dist; ca.decay_rate = c->decay_rate; ca.moving_speed_th = c->moving_speed_th;
-            HIPCK(h, launch_agent_collision(ca, s));
-            g.ext_grad = w.col_grad;
+        if (terms & TERM_COLLISION) {
+            HIPCK(h, launch_agent_collision(collision_args(gd->collision, w.col_traj, gin, nullptr, w.col_grad, B), s));
+            gin = w.col_grad;
         }
-        if (gd->map_collision) {                     // adds to whatever gradient is there already (caller's ext_grad, agent collisions)
-            HIPCK(h, launch_map_collision(map_args(h, gd->map_collision, w.col_traj, gd->collision ? w.col_grad : gd->ext_grad, nullptr, w.col_grad), B, s));
-            g.ext_grad = w.col_grad;
+        if (terms & TERM_MAP) {
+            HIPCK(h, launch_map_collision(map_args(h, gd->map_collision, w.col_traj, gin, nullptr, w.col_grad), B, s));
+            gin = w.col_grad;
         }
-        if (h->has_goal) {                           // likewise: on top of the caller's ext_grad and the collision gradients
-            HIPCK(h, launch_goal(goal_args(&h->goal, w.col_traj, (gd->collision || gd->map_collision) ? w.col_grad : gd->ext_grad, nullptr, w.col_grad, B), s));
-            g.ext_grad = w.col_grad;
+        if (terms & TERM_GOAL) {
+            HIPCK(h, launch_goal(goal_args(&h->goal, w.col_traj, gin, nullptr, w.col_grad, B), s));
+            gin = w.col_grad;
         }
-        if (h->has_social) {                         // after the goal term's: evaluation (loop iteration, optimiser step) picks the draws
-            const float* gin = (gd->collision || gd->map_collision || h->has_goal) ? w.col_grad : gd->ext_grad;
+        if (terms & TERM_SOCIAL) {                       // evaluation (loop iteration, optimiser step) picks the draws
             HIPCK(h, launch_social_group(social_args(&h->social, w.col_traj, nullptr, w.col_grad, B, (int)salt, k - 1), gin, s));
-            g.ext_grad = w.col_grad;
+            gin = w.col_grad;
         }
-        if (h->has_pair) {                           // after the social term's, on the same decoded iterate
-            const float* gin = (gd->collision || gd->map_collision || h->has_goal || h->has_social) ? w.col_grad : gd->ext_grad;
+        if (terms & TERM_PAIR) {
             HIPCK(h, launch_pair(pair_args(&h->pair, w.col_traj, nullptr, w.col_grad, B), gin, s));
-            g.ext_grad = w.col_grad;
+            gin = w.col_grad;
         }
-        if (h->has_lane) {                           // after the pair term's, on the same decoded iterate
-            const float* gin = (gd->collision || gd->map_collision || h->has_goal || h->has_social || h->has_pair) ? w.col_grad : gd->ext_grad;
+        if (terms & TERM_LANE) {
             HIPCK(h, launch_lane(lane_args(&h->lane, w.col_traj, nullptr, nullptr, w.col_grad, B), gin, s));
-            g.ext_grad = w.col_grad;
+            gin = w.col_grad;
         }
+        g.ext_grad = gin;
         g.z = last ? z : nullptr;
         g.sigma = last ? sigma_noise : 0.f;
         g.mean_out = last ? mean_out : w.gcur;           // in place from step 2 on: a workgroup reads its agents' rows before it writes them
@@ -1786,13 +1803,7 @@ static int sample_impl(cld_handle h, const char* fn, const float* x_T, const flo
     // both halves the same latent; the head combines the two noise predictions and rewrites both halves.
     const int bp = pad16(B), bpn = cfg ? 2 * bp : bp;
     Ws w = carve(workspace, bpn);
-    float* x_hi = w.xw + (size_t)bp * T * D;
-    HIPCK(h, launch_pack_latent(x_T, w.xw, B, bp, s));
-    HIPCK(h, launch_cond_bias(cond, h->wc, h->cbias_b, w.cb, B, bp, NCB, s));
-    if (cfg) {
-        HIPCK(h, launch_pack_latent(x_T, x_hi, B, bp, s));
-        HIPCK(h, launch_cond_bias(non_cond, h->wc, h->cbias_b, w.cb + (size_t)bp * NCB, B, bp, NCB, s));
-    }
+    if ((rc = load_inputs(h, w, B, bp, x_T, cond, non_cond, cfg, s)) != CLD_OK) return rc;
     for (int it = 0; it < steps; ++it) {
         const int i = (steps - 1 - it) * h->stride;
         rc = sample_iteration(h, w, cfg, B, bp, i, noise ? noise + (size_t)it * B * T * D : nullptr, seed, (unsigned long long)it, cond,
@@ -1819,12 +1830,7 @@ int cld_sample_step(cld_handle h, const float* x_t, const float* cond, const flo
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int bp = pad16(B), bpn = cfg ? 2 * bp : bp;
     Ws w = carve(workspace, bpn);
-    HIPCK(h, launch_pack_latent(x_t, w.xw, B, bp, s));
-    HIPCK(h, launch_cond_bias(cond, h->wc, h->cbias_b, w.cb, B, bp, NCB, s));
-    if (cfg) {
-        HIPCK(h, launch_pack_latent(x_t, w.xw + (size_t)bp * T * D, B, bp, s));
-        HIPCK(h, launch_cond_bias(non_cond, h->wc, h->cbias_b, w.cb + (size_t)bp * NCB, B, bp, NCB, s));
-    }
+    if ((rc = load_inputs(h, w, B, bp, x_t, cond, non_cond, cfg, s)) != CLD_OK) return rc;
     rc = sample_iteration(h, w, cfg, B, bp, t_idx, z, 0, 0, cond, guidance_w, gd, mean_guided, grad, mean != nullptr, s);
     if (rc) return rc;
     if (x_next) HIPCK(h, launch_unpack(w.xw, x_next, B, s));
@@ -1870,11 +1876,7 @@ int cld_guidance_losses(cld_handle h, const float* traj, const cld_guidance* gd,
     if (!h) return CLD_ERR_ARG;
     if (!traj || !gd || !losses || B < 1) return fail(h, CLD_ERR_ARG, "cld_guidance_losses: bad argument");
     if (gd->target_pos_scale && (!gd->target_pos || !gd->target_time)) return fail(h, CLD_ERR_ARG, "cld_guidance_losses: target_pos_scale needs target_pos and target_time");
-    GuideArgs g{};
-    g.target_speed = gd->target_speed; g.loss_scale = gd->loss_scale;
-    g.speed_limit_scale = gd->speed_limit_scale; g.acc_limit_scale = gd->acc_limit_scale;
-    g.speed_limit = gd->speed_limit; g.acc_limit = gd->acc_limit;
-    g.target_pos = gd->target_pos; g.target_time = gd->target_time; g.target_pos_scale = gd->target_pos_scale;
+    GuideArgs g = builtin_terms(gd);
     g.B = B;
     HIPCK(h, launch_guide_losses(g, traj, losses, static_cast<hipStream_t>(stream)));
     return CLD_OK;
@@ -1888,8 +1890,7 @@ int cld_log_prob(cld_handle h, const float* x_t, const float* x_tm1, const float
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int bp = pad16(M);
     Ws w = carve(workspace, bp);
-    HIPCK(h, launch_pack_latent(x_t, w.xw, M, bp, s));
-    HIPCK(h, launch_cond_bias(cond, h->wc, h->cbias_b, w.cb, M, bp, NCB, s));
+    if ((rc = load_inputs(h, w, M, bp, x_t, cond, nullptr, false, s)) != CLD_OK) return rc;
     HIPCK(h, run_unet(h, w, w.xw, t_idx, bp, s));
     HeadArgs a{};
     head_source(h, w, a); a.w = h->head_w; a.b = h->head_b; a.x = w.xw; a.B = M; a.b_pad = bp;
@@ -2113,12 +2114,7 @@ int cld_agent_collision(cld_handle h, const float* traj, const cld_collision* c,
     if (!traj || !c || B < 1 || (!loss && !grad)) return fail(h, CLD_ERR_ARG, "cld_agent_collision: bad argument");
     int rc = check_collision(h, "cld_agent_collision", c, B);
     if (rc) return rc;
-    CollisionArgs ca{};
-    ca.traj = traj; ca.extent = c->extent; ca.world_from_agent = c->world_from_agent; ca.curr_speed = c->curr_speed;
-    ca.scene_start = c->scene_start; ca.scene_weight = c->scene_weight; ca.guided = c->guided; ca.excluded = c->excluded; ca.max_scene_agents = c->max_scene_agents; ca.grad_in = grad_in;
-    ca.loss = loss; ca.grad = grad; ca.B_agents = B / c->num_samp; ca.num_scenes = c->num_scenes; ca.num_samp = c->num_samp;
-    ca.num_disks = c->num_disks; ca.buffer_dist = c->buffer_dist; ca.decay_rate = c->decay_rate; ca.moving_speed_th = c->moving_speed_th;
-    HIPCK(h, launch_agent_collision(ca, static_cast<hipStream_t>(stream)));
+    HIPCK(h, launch_agent_collision(collision_args(c, traj, grad_in, loss, grad, B), static_cast<hipStream_t>(stream)));
     return CLD_OK;
 }
 
@@ -2152,12 +2148,7 @@ int cld_social_group_loss(cld_handle h, const float* traj, const cld_social_grou
     return CLD_OK;
 }
 
-int cld_set_social_term(cld_handle h, const cld_social_group* term) {
-    if (!h) return CLD_ERR_ARG;
-    h->has_social = term != nullptr;
-    h->social = term ? *term : cld_social_group{};
-    return CLD_OK;
-}
+int cld_set_social_term(cld_handle h, const cld_social_group* term) { return set_term(h, term, &cld_handle_s::social, &cld_handle_s::has_social); }
 
 int cld_pair_loss(cld_handle h, const float* traj, const cld_pair_term* term, const float* grad_in, float* value, float* grad, int32_t B,
                   void* stream) {
@@ -2169,12 +2160,7 @@ int cld_pair_loss(cld_handle h, const float* traj, const cld_pair_term* term, co
     return CLD_OK;
 }
 
-int cld_set_pair_term(cld_handle h, const cld_pair_term* term) {
-    if (!h) return CLD_ERR_ARG;
-    h->has_pair = term != nullptr;
-    h->pair = term ? *term : cld_pair_term{};
-    return CLD_OK;
-}
+int cld_set_pair_term(cld_handle h, const cld_pair_term* term) { return set_term(h, term, &cld_handle_s::pair, &cld_handle_s::has_pair); }
 
 int cld_lane_prepare(cld_handle h, const double* world_lines, const int32_t* line_frame, const float* agent_from_world, float* lines,
                      int32_t num_lines, int32_t max_pts, int32_t num_frames, void* stream) {
@@ -2200,19 +2186,9 @@ int cld_lane_loss(cld_handle h, const float* traj, const cld_lane_term* term, co
     return CLD_OK;
 }
 
-int cld_set_lane_term(cld_handle h, const cld_lane_term* term) {
-    if (!h) return CLD_ERR_ARG;
-    h->has_lane = term != nullptr;
-    h->lane = term ? *term : cld_lane_term{};
-    return CLD_OK;
-}
+int cld_set_lane_term(cld_handle h, const cld_lane_term* term) { return set_term(h, term, &cld_handle_s::lane, &cld_handle_s::has_lane); }
 
-int cld_set_goal_term(cld_handle h, const cld_goal* g) {
-    if (!h) return CLD_ERR_ARG;
-    h->has_goal = g != nullptr;
-    h->goal = g ? *g : cld_goal{};
-    return CLD_OK;
-}
+int cld_set_goal_term(cld_handle h, const cld_goal* g) { return set_term(h, g, &cld_handle_s::goal, &cld_handle_s::has_goal); }
 
 int cld_set_map_source(cld_handle h, const cld_map_source* m) {
     if (!h) return CLD_ERR_ARG;
@@ -2226,9 +2202,7 @@ int cld_set_map_source(cld_handle h, const cld_map_source* m) {
                         (int64_t)m->map_h * m->map_w > INT32_MAX))
             return fail(h, CLD_ERR_ARG, "cld_set_map_source: maps need scene_map, map_from_world, num_maps, map_h and map_w");
     }
-    h->has_map_source = m != nullptr;
-    h->map_source = m ? *m : cld_map_source{};
-    return CLD_OK;
+    return set_term(h, m, &cld_handle_s::map_source, &cld_handle_s::has_map_source);
 }
 
 int cld_world_step(cld_handle h, const float* traj, const float* centroid, const float* yaw, int32_t k, float* world,
@@ -2797,8 +2771,7 @@ static int recon_prepare(cld_handle h, const Ws& w, const ReconWs& r, bool cfg, 
 static int recon_last(cld_handle h, const Ws& w, const ReconWs& r, bool cfg, int B, const float* z, uint64_t seed, unsigned long long salt,
                       const float* cond, float guidance_w, hipStream_t s) {
     const int bp = pad16(B);
-    HIPCK(h, launch_pack_latent(r.xt, w.xw, B, bp, s));
-    if (cfg) HIPCK(h, launch_pack_latent(r.xt, w.xw + (size_t)bp * T * D, B, bp, s));
+    if (int r0 = load_inputs(h, w, B, bp, r.xt, nullptr, nullptr, cfg, s)) return r0;
     return sample_iteration(h, w, cfg, B, bp, 0, z, seed, salt, cond, guidance_w, nullptr, nullptr, nullptr, false, s);
 }
 

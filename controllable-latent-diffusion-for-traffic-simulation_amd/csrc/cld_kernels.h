@@ -18,6 +18,14 @@ inline hipError_t set_max_lds_once(const void* fn, int bytes, unsigned long long
     return hipSuccess;
 }
 
+// What the launchers of the terms whose kernels ADD to `grad` [rows, 52, 6] do first: grad = grad_in, or 0 without one -- unless the
+// two alias (or no gradient is asked for), where there is nothing to do.
+inline hipError_t seed_grad(float* grad, const float* grad_in, int rows, hipStream_t s) {
+    if (!grad || grad == grad_in) return hipSuccess;
+    const size_t bytes = (size_t)rows * 52 * 6 * sizeof(float);
+    return grad_in ? hipMemcpyAsync(grad, grad_in, bytes, hipMemcpyDeviceToDevice, s) : hipMemsetAsync(grad, 0, bytes, s);
+}
+
 // ---------------------------------------------------------------------------
 // Activation layout in HBM: channels-last [B_pad, L, C] fp32, B_pad = B rounded
 // up to 16 agents.  All three U-Net resolutions hold 3,328 floats per agent at

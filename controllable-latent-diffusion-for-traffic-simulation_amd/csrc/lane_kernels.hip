@@ -27,6 +27,7 @@
 // polyline has no segment with a finite, non-zero length, is not evaluated (NaN value, NaN projection, no contribution).  NOT checked:
 // that an agent's entries are contiguous -- an agent in two separate runs stays inside the arrays, but two workgroups then add to
 // one row and its bits are no longer the same on every run; the order is the caller's contract (Engine._lane refuses such a term).
+#include "cld_kernels.h"
 #include "lane_kernels.h"
 
 namespace cld {
@@ -235,11 +236,7 @@ hipError_t launch_lane(const LaneArgs& a, const float* grad_in, hipStream_t s) {
         return hipErrorInvalidValue;
     const long long blocks = (long long)a.num_entries * a.num_samp;
     if (blocks > INT32_MAX) return hipErrorInvalidValue;
-    if (a.grad && a.grad != grad_in) {                                   // rows without an entry: the gradient of grad_in (or 0)
-        const size_t bytes = (size_t)a.rows * TT * 6 * sizeof(float);
-        const hipError_t e = grad_in ? hipMemcpyAsync(a.grad, grad_in, bytes, hipMemcpyDeviceToDevice, s) : hipMemsetAsync(a.grad, 0, bytes, s);
-        if (e != hipSuccess) return e;
-    }
+    if (const hipError_t e = seed_grad(a.grad, grad_in, a.rows, s); e != hipSuccess) return e;      // rows without an entry: the gradient of grad_in (or 0)
     hipLaunchKernelGGL(lane_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, s, a);
     return hipGetLastError();
 }

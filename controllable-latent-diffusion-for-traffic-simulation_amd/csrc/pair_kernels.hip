@@ -161,11 +161,7 @@ hipError_t launch_pair(const PairArgs& a, const float* grad_in, hipStream_t s) {
     const long long value_items = a.value ? (long long)a.num_pairs * a.num_samp : 0;
     const long long grad_blocks = (grad_items + kThreads - 1) / kThreads, value_blocks = (value_items + kWaves - 1) / kWaves;
     if (grad_items > INT32_MAX || value_items > INT32_MAX || grad_blocks + value_blocks > INT32_MAX) return hipErrorInvalidValue;
-    if (a.grad && a.grad != grad_in) {                                   // rows in no pair: the gradient of grad_in (or 0)
-        const size_t bytes = (size_t)a.rows * TT * 6 * sizeof(float);
-        const hipError_t e = grad_in ? hipMemcpyAsync(a.grad, grad_in, bytes, hipMemcpyDeviceToDevice, s) : hipMemsetAsync(a.grad, 0, bytes, s);
-        if (e != hipSuccess) return e;
-    }
+    if (const hipError_t e = seed_grad(a.grad, grad_in, a.rows, s); e != hipSuccess) return e;      // rows in no pair: the gradient of grad_in (or 0)
     if (grad_blocks + value_blocks == 0) return hipSuccess;
     hipLaunchKernelGGL(pair_kernel, dim3((unsigned)(grad_blocks + value_blocks)), dim3(kThreads), 0, s, a, (int)grad_blocks);
     return hipGetLastError();

@@ -178,11 +178,7 @@ hipError_t launch_social_group(const SocialArgs& a, const float* grad_in, hipStr
         const hipError_t e = hipMemsetAsync(a.loss, 0, (size_t)a.rows * sizeof(float), s);
         if (e != hipSuccess) return e;
     }
-    if (a.grad && a.grad != grad_in) {
-        const size_t bytes = (size_t)a.rows * TT * 6 * sizeof(float);
-        const hipError_t e = grad_in ? hipMemcpyAsync(a.grad, grad_in, bytes, hipMemcpyDeviceToDevice, s) : hipMemsetAsync(a.grad, 0, bytes, s);
-        if (e != hipSuccess) return e;
-    }
+    if (const hipError_t e = seed_grad(a.grad, grad_in, a.rows, s); e != hipSuccess) return e;
     // about one (step, member) item per thread in the gradient role: 52 steps for a group of 4, 4 for one of 64, 2 for one of 128
     const int Ms = a.max_members | 1;
     const int steps_per_wg = std::min(TT, std::max(1, kThreads / a.max_members));

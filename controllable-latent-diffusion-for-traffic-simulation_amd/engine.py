@@ -103,6 +103,11 @@ def vae_param_table(lib=None, h=None):
     return _param_table(lib, h, "vae")
 
 
+# what a guided call reads from the handle, in the order it is set: (guidance dict key, Engine builder, library setter)
+_HANDLE_TERMS = (("goal", "_goal", "cld_set_goal_term"), ("social_group", "_social", "cld_set_social_term"), ("pair", "_pair", "cld_set_pair_term"),
+                 ("lane", "_lane", "cld_set_lane_term"), ("map_collision", "_map_source", "cld_set_map_source"))
+
+
 class Engine:
     """Owns a `cld_handle`.  Weights come in under the reference's state_dict names."""
 
@@ -178,6 +183,12 @@ class Engine:
         if shape is not None and tuple(t.shape) != tuple(shape):
             raise CldError(f"expected shape {tuple(shape)}, got {tuple(t.shape)}")
         return t
+
+    def _per(self, v, n: int, div: float = 1.0) -> torch.Tensor:
+        """A scalar weight (divided by `div`) for all n, or a tensor / sequence of length n as it is -> float32 [n] on the device."""
+        if not isinstance(v, torch.Tensor) and np.isscalar(v):
+            return torch.full((n,), float(v) / div, device=self.device)
+        return self._f32(torch.as_tensor(v, dtype=torch.float32), (n,))
 
     def __del__(self):
         try:
@@ -380,9 +391,7 @@ class Engine:
             v = g.get(key)
             if v is None:
                 return 0.0, None
-            lim, sc = v
-            sc = torch.full((B,), float(sc) / T, device=self.device) if not isinstance(sc, torch.Tensor) and np.isscalar(sc) else self._f32(sc, (B,))
-            return float(lim), sc
+            return float(v[0]), self._per(v[1], B, T)
         sl, sls = term("speed_limit")
         al, als = term("acc_limit")
         eg = None if g.get("ext_grad") is None else self._f32(g["ext_grad"], (B, T, 6))
@@ -393,7 +402,7 @@ class Engine:
             tt = torch.as_tensor(time_).to(self.device, torch.int32).contiguous()
             if tuple(tt.shape) != (B,):
                 raise CldError(f"target_pos time index: expected shape ({B},), got {tuple(tt.shape)}")
-            tps = torch.full((B,), float(sc), device=self.device) if not isinstance(sc, torch.Tensor) and np.isscalar(sc) else self._f32(sc, (B,))
+            tps = self._per(sc, B)
         th = g.get("perturb_th")
         opt = g.get("optimizer", "adam")
         if opt not in _lib.OPTIMIZERS:
@@ -435,18 +444,10 @@ class Engine:
             raise CldError(f"agent_collision: {B} rows are not a multiple of num_samp = {N}")
         A = B // N
         ext = self._f32(c["extent"], (A, 3)); wfa = self._f32(c["world_from_agent"], (A, 3, 3)); spd = self._f32(c["curr_speed"], (A,))
-        if c.get("scene_sizes") is not None:
-            sizes = [int(v) for v in c["scene_sizes"]]
-        else:
-            si = torch.as_tensor(c["scene_index"]).cpu()
-            _, counts = torch.unique_consecutive(si, return_counts=True)
-            sizes = [int(v) for v in counts]
-        if sum(sizes) != A or min(sizes) < 1:
-            raise CldError(f"agent_collision: scene sizes {sizes} do not cover the {A} agents")
+        if c.get("scene_sizes") is None and c.get("scene_index") is None:       # (one scene by default is the map term's)
+            raise CldError("agent_collision: needs scene_sizes or scene_index")
+        sizes, start, wts = self._scene_blocks(c, A, "agent_collision")
         S = len(sizes)
-        start = torch.tensor(np.concatenate([[0], np.cumsum(sizes)]), dtype=torch.int32, device=self.device)
-        wv = c.get("weight", 1.0)
-        wts = torch.full((S,), float(wv), device=self.device) if np.isscalar(wv) else self._f32(torch.as_tensor(wv, dtype=torch.float32), (S,))
         guided = None
         if c.get("agents"):
             gm = np.zeros(A, np.uint8)
@@ -484,9 +485,7 @@ class Engine:
         if sum(sizes) != A or min(sizes) < 1:
             raise CldError(f"{what}: scene sizes {sizes} do not cover the {A} agents")
         start = torch.tensor(np.concatenate([[0], np.cumsum(sizes)]), dtype=torch.int32, device=self.device)
-        wv = c.get("weight", 1.0)
-        wts = torch.full((len(sizes),), float(wv), device=self.device) if np.isscalar(wv) else self._f32(torch.as_tensor(wv, dtype=torch.float32), (len(sizes),))
-        return sizes, start, wts
+        return sizes, start, self._per(c.get("weight", 1.0), len(sizes))
 
     def _map_collision(self, c: Mapping, B: int):
         """dict(extent [A,3], raster_from_agent [A,3,3], drivable_map [A,H,W] (non-zero = drivable), curr_speed [A], scene_index |
@@ -495,7 +494,7 @@ class Engine:
         (src/tbsim/utils/guidance_loss.py:717-875).  In place of `drivable_map`: map_source = dict(maps, scene_map, map_from_world,
         world [A,3], drivable_layer = 0, height, width, px_per_m, ego_center, no_map_fill as RASTER_DEFAULTS names them) --
         the term then reads the scene maps themselves (H, W = height, width) and the struct has no drivable_map; the source goes to
-        the handle around the library call (_map_source_term)."""
+        the handle around the library call (_handle_terms)."""
         N = int(c.get("num_samp", 1))
         if B % N:
             raise CldError(f"map_collision: {B} rows are not a multiple of num_samp = {N}")
@@ -564,18 +563,24 @@ class Engine:
         return src, (mp, sm, mfw, world)
 
     @contextlib.contextmanager
-    def _map_source_term(self, mc: Optional[Mapping], B: int):
-        """The `map_source` of a map_collision dict kept on the handle for the library call inside (cld_set_map_source), and cleared
-        behind it whatever happens: no source outlives the call that set it."""
-        if mc is None or mc.get("map_source") is None:
-            yield
-            return
-        src, keep = self._map_source(mc, B)
-        self._check(self.lib.cld_set_map_source(self._h, C.byref(src)), "cld_set_map_source")
+    def _handle_terms(self, guidance: Optional[Mapping], B: int):
+        """The entries of a guidance dict that are not part of the cld_guidance struct -- goal, social_group, pair, lane, and the
+        `map_source` of a map_collision entry (_HANDLE_TERMS) -- kept on the handle for the library call inside (cld_set_*), in that
+        order, and cleared behind it whatever happens, a builder or setter further down the list raising included: no term outlives the
+        call that set it.  (World-frame lane polylines are prepared once, here, for the whole call.)"""
+        held = []                                        # (setter, struct, tensors kept alive)
         try:
+            for key, build, setter in _HANDLE_TERMS:
+                c = None if guidance is None else guidance.get(key)
+                if c is None or (key == "map_collision" and c.get("map_source") is None):
+                    continue
+                cs, keep = getattr(self, build)(c, B)
+                self._check(getattr(self.lib, setter)(self._h, C.byref(cs)), setter)
+                held.append((setter, cs, keep))
             yield
         finally:
-            self.lib.cld_set_map_source(self._h, None)
+            for setter, _, _ in reversed(held):
+                getattr(self.lib, setter)(self._h, None)
 
     def _goal(self, c: Mapping, B: int):
         """dict(kind [A] (0 off | 1 global_target_pos | 2 global_target_pos_at_time, _lib.GOAL_KINDS), target_pos [A,2] (world),
@@ -610,21 +615,6 @@ class Engine:
                           float(c.get("min_progress_dist", 0.5)))
         return cg, (tp, afw, kind, tt, urg, ps, sc, rd)
 
-    @contextlib.contextmanager
-    def _goal_term(self, guidance: Optional[Mapping], B: int):
-        """The `goal` entry of a guidance dict kept on the handle for the library call inside (cld_set_goal_term), and cleared
-        behind it whatever happens: no term outlives the call that set it."""
-        g = None if guidance is None else guidance.get("goal")
-        if g is None:
-            yield
-            return
-        cg, keep = self._goal(g, B)
-        self._check(self.lib.cld_set_goal_term(self._h, C.byref(cg)), "cld_set_goal_term")
-        try:
-            yield
-        finally:
-            self.lib.cld_set_goal_term(self._h, None)
-
     def _social(self, c: Mapping, B: int):
         """dict(groups: one list of agent indices per group (each sorted ascending here), leader: per group an agent (batch) index | -1
         | None, social_dist = 1.5 and cohesion = 0.8: scalar or per group, scale [G] (d total / d value of a member row: weight /
@@ -653,11 +643,7 @@ class Engine:
         if len(ld) != G:
             raise CldError(f"social_group leader: expected {G} entries, got {len(ld)}")
         leader = torch.tensor(ld, dtype=torch.int32, device=self.device)
-
-        def per_group(key, default):
-            v = c.get(key, default)
-            return torch.full((G,), float(v), device=self.device) if np.isscalar(v) else self._f32(torch.as_tensor(v, dtype=torch.float32), (G,))
-        sd, coh = per_group("social_dist", 1.5), per_group("cohesion", 0.8)
+        sd, coh = self._per(c.get("social_dist", 1.5), G), self._per(c.get("cohesion", 0.8), G)
         sc = self._f32(torch.as_tensor(c["scale"], dtype=torch.float32), (G,))
         wfa = self._f32(c["world_from_agent"], (A, 3, 3))
         dr = du = None
@@ -679,34 +665,28 @@ class Engine:
                                  int(c.get("iter_base", 0)), n_iter, n_opt)
         return cs, (start, member, leader, sd, coh, sc, wfa, dr, du)
 
-    @contextlib.contextmanager
-    def _social_term(self, guidance: Optional[Mapping], B: int):
-        """The `social_group` entry of a guidance dict kept on the handle for the library call inside (cld_set_social_term), and
-        cleared behind it whatever happens: no term outlives the call that set it."""
-        g = None if guidance is None else guidance.get("social_group")
-        if g is None:
-            yield
-            return
-        cs, keep = self._social(g, B)
-        self._check(self.lib.cld_set_social_term(self._h, C.byref(cs)), "cld_set_social_term")
-        try:
-            yield
-        finally:
-            self.lib.cld_set_social_term(self._h, None)
+    def _plan_loss(self, call: str, build, traj, cfg: Mapping, grad_in, want_grad: bool, shape=None, want_proj=None, terms=None):
+        """What the six stand-alone losses on decoded plans [B,52,6] share: shape the plans, `build(cfg, B)` -> the term's struct, the
+        optional grad_in [B,52,6], the outputs -- values [B], or `shape(struct)`; the gradient if wanted; the projections [*shape,52,3] of a
+        call that has them (want_proj not None) if wanted -- and the library call -> (values, gradient | None, projections | None)."""
+        traj = self._f32(traj)
+        B = traj.shape[0]
+        traj = self._f32(traj, (B, T, 6))
+        cs, keep = build(cfg, B)
+        gi = None if grad_in is None else self._f32(grad_in, (B, T, 6))
+        vshape = shape(cs) if shape else (B,)
+        value = torch.empty(*vshape, dtype=torch.float32, device=self.device)
+        grad = torch.empty(B, T, 6, dtype=torch.float32, device=self.device) if want_grad else None
+        proj = torch.empty(*vshape, T, 3, dtype=torch.float32, device=self.device) if want_proj else None
+        outs = (_ptr(value),) + (() if want_proj is None else (_ptr(proj),)) + (_ptr(grad),)
+        with torch.cuda.device(self.device), self._handle_terms(terms, B):
+            self._check(getattr(self.lib, call)(self._h, _ptr(traj), C.byref(cs), _ptr(gi), *outs, B, self._stream()), call)
+        return value, grad, proj
 
     def social_group_loss(self, traj, term: Mapping, grad_in=None, want_grad=True):
         """Upstream's SocialGroupLoss on decoded plans [B,52,6] (descaled, sample-minor rows; `term`: see _social) -> (per-row values
         [B], 0 outside the groups, grad_in + d total / d traj [B,52,6]); cld_social_group_loss.  Caller draws: slab [0, 0]."""
-        traj = self._f32(traj)
-        B = traj.shape[0]
-        traj = self._f32(traj, (B, T, 6))
-        cs, keep = self._social(term, B)
-        gi = None if grad_in is None else self._f32(grad_in, (B, T, 6))
-        loss = torch.empty(B, dtype=torch.float32, device=self.device)
-        grad = torch.empty(B, T, 6, dtype=torch.float32, device=self.device) if want_grad else None
-        with torch.cuda.device(self.device):
-            self._check(self.lib.cld_social_group_loss(self._h, _ptr(traj), C.byref(cs), _ptr(gi), _ptr(loss), _ptr(grad), B, self._stream()),
-                        "cld_social_group_loss")
+        loss, grad, _ = self._plan_loss("cld_social_group_loss", self._social, traj, term, grad_in, want_grad)
         return (loss, grad) if want_grad else loss
 
     def _pair(self, c: Mapping, B: int):
@@ -743,12 +723,8 @@ class Engine:
             raise CldError(f"pair kind {e.args[0]!r}: one of {sorted(_lib.PAIR_KINDS)}") from None
         if any(k not in _lib.PAIR_KINDS.values() for k in kd):
             raise CldError(f"pair kind: numbers {sorted(_lib.PAIR_KINDS.values())}")
-
-        def per_pair(key, default=0.0):
-            v = c.get(key, default)
-            return torch.full((P,), float(v), device=self.device) if np.isscalar(v) else self._f32(torch.as_tensor(v, dtype=torch.float32), (P,))
-        lo, hi, dec = per_pair("lo"), per_pair("hi"), per_pair("decay")
-        sc = per_pair("scale") if c.get("scale") is not None else per_pair("weight") / N
+        lo, hi, dec = (self._per(c.get(k, 0.0), P) for k in ("lo", "hi", "decay"))
+        sc = self._per(c["scale"], P) if c.get("scale") is not None else self._per(c["weight"], P) / N
         wfa = self._f32(c["world_from_agent"], (A, 3, 3))
         afw = None if c.get("agent_from_world") is None else self._f32(c["agent_from_world"], (A, 3, 3))
         ids, start, inc = pair_incidences(tg, rf, A)
@@ -759,34 +735,10 @@ class Engine:
                               P, N, len(ids), len(inc))
         return cs, (tgt, reft, kind, lo, hi, dec, sc, wfa, afw, start_t, ids_t, inc_t)
 
-    @contextlib.contextmanager
-    def _pair_term(self, guidance: Optional[Mapping], B: int):
-        """The `pair` entry of a guidance dict kept on the handle for the library call inside (cld_set_pair_term), and cleared behind
-        it whatever happens: no term outlives the call that set it."""
-        g = None if guidance is None else guidance.get("pair")
-        if g is None:
-            yield
-            return
-        cs, keep = self._pair(g, B)
-        self._check(self.lib.cld_set_pair_term(self._h, C.byref(cs)), "cld_set_pair_term")
-        try:
-            yield
-        finally:
-            self.lib.cld_set_pair_term(self._h, None)
-
     def pair_loss(self, traj, term: Mapping, grad_in=None, want_grad=True):
         """Upstream's pair-relation losses on decoded plans [B,52,6] (descaled, sample-minor rows; `term`: see _pair) -> (values
         [P, num_samp] as upstream's classes return them, grad_in + d total / d traj [B,52,6]); cld_pair_loss."""
-        traj = self._f32(traj)
-        B = traj.shape[0]
-        traj = self._f32(traj, (B, T, 6))
-        cs, keep = self._pair(term, B)
-        gi = None if grad_in is None else self._f32(grad_in, (B, T, 6))
-        value = torch.empty(cs.num_pairs, cs.num_samp, dtype=torch.float32, device=self.device)
-        grad = torch.empty(B, T, 6, dtype=torch.float32, device=self.device) if want_grad else None
-        with torch.cuda.device(self.device):
-            self._check(self.lib.cld_pair_loss(self._h, _ptr(traj), C.byref(cs), _ptr(gi), _ptr(value), _ptr(grad), B, self._stream()),
-                        "cld_pair_loss")
+        value, grad, _ = self._plan_loss("cld_pair_loss", self._pair, traj, term, grad_in, want_grad, shape=lambda cs: (cs.num_pairs, cs.num_samp))
         return (value, grad) if want_grad else value
 
     def lane_prepare(self, world_lines, line_frame, agent_from_world):
@@ -865,93 +817,38 @@ class Engine:
             raise CldError(f"lane kind {e.args[0]!r}: one of {sorted(_lib.LANE_KINDS)}") from None
         if any(k not in _lib.LANE_KINDS.values() for k in kd):
             raise CldError(f"lane kind: numbers {sorted(_lib.LANE_KINDS.values())}")
-
-        def per_entry(key, default=0.0):
-            v = c.get(key, default)
-            return torch.full((E,), float(v), device=self.device) if np.isscalar(v) else self._f32(torch.as_tensor(v, dtype=torch.float32), (E,))
-        dec = per_entry("decay", 0.9)
-        sc = per_entry("scale") if c.get("scale") is not None else per_entry("weight") / N
+        dec = self._per(c.get("decay", 0.9), E)
+        sc = self._per(c["scale"], E) if c.get("scale") is not None else self._per(c["weight"], E) / N
         i32 = lambda v: torch.tensor(v, dtype=torch.int32, device=self.device)
         agt, lnt, kind = i32(ag), i32(ln), i32(kd)
         cs = _lib.CldLaneTerm(lines.data_ptr(), agt.data_ptr(), lnt.data_ptr(), kind.data_ptr(), dec.data_ptr(), sc.data_ptr(), E, L,
                               int(lines.shape[1]), N)
         return cs, (lines, agt, lnt, kind, dec, sc)
 
-    @contextlib.contextmanager
-    def _lane_term(self, guidance: Optional[Mapping], B: int):
-        """The `lane` entry of a guidance dict kept on the handle for the library call inside (cld_set_lane_term; world-frame
-        polylines are prepared once, here, for the whole call), and cleared behind it whatever happens."""
-        g = None if guidance is None else guidance.get("lane")
-        if g is None:
-            yield
-            return
-        cs, keep = self._lane(g, B)
-        self._check(self.lib.cld_set_lane_term(self._h, C.byref(cs)), "cld_set_lane_term")
-        try:
-            yield
-        finally:
-            self.lib.cld_set_lane_term(self._h, None)
-
     def lane_loss(self, traj, term: Mapping, grad_in=None, want_grad=True, want_proj=False):
         """Upstream's lane-projection losses on decoded plans [B,52,6] (descaled, sample-minor rows; `term`: see _lane) -> values
         [E, num_samp] (unweighted) [, grad_in + d total / d traj [B,52,6]] [, the projections [E, num_samp, 52, 3]]; cld_lane_loss."""
-        traj = self._f32(traj)
-        B = traj.shape[0]
-        traj = self._f32(traj, (B, T, 6))
-        cs, keep = self._lane(term, B)
-        gi = None if grad_in is None else self._f32(grad_in, (B, T, 6))
-        value = torch.empty(cs.num_entries, cs.num_samp, dtype=torch.float32, device=self.device)
-        grad = torch.empty(B, T, 6, dtype=torch.float32, device=self.device) if want_grad else None
-        proj = torch.empty(cs.num_entries, cs.num_samp, T, 3, dtype=torch.float32, device=self.device) if want_proj else None
-        with torch.cuda.device(self.device):
-            self._check(self.lib.cld_lane_loss(self._h, _ptr(traj), C.byref(cs), _ptr(gi), _ptr(value), _ptr(proj), _ptr(grad), B, self._stream()),
-                        "cld_lane_loss")
+        value, grad, proj = self._plan_loss("cld_lane_loss", self._lane, traj, term, grad_in, want_grad, shape=lambda cs: (cs.num_entries, cs.num_samp),
+                                            want_proj=bool(want_proj))
         out = (value,) + ((grad,) if want_grad else ()) + ((proj,) if want_proj else ())
         return out if len(out) > 1 else value
 
     def goal_loss(self, traj, goal: Mapping, grad_in=None, want_grad=True):
         """Upstream's global waypoint losses on decoded plans [B,52,6] (descaled, sample-minor rows; `goal`: see _goal) ->
         (per-row values [B] as upstream files them under guide_losses, grad_in + scale * d value / d traj [B,52,6]); cld_goal_loss."""
-        traj = self._f32(traj)
-        B = traj.shape[0]
-        traj = self._f32(traj, (B, T, 6))
-        cg, keep = self._goal(goal, B)
-        gi = None if grad_in is None else self._f32(grad_in, (B, T, 6))
-        loss = torch.empty(B, dtype=torch.float32, device=self.device)
-        grad = torch.empty(B, T, 6, dtype=torch.float32, device=self.device) if want_grad else None
-        with torch.cuda.device(self.device):
-            self._check(self.lib.cld_goal_loss(self._h, _ptr(traj), C.byref(cg), _ptr(gi), _ptr(loss), _ptr(grad), B, self._stream()),
-                        "cld_goal_loss")
+        loss, grad, _ = self._plan_loss("cld_goal_loss", self._goal, traj, goal, grad_in, want_grad)
         return (loss, grad) if want_grad else loss
 
     def map_collision(self, traj, cfg: Mapping, grad_in=None, want_grad=True):
         """Upstream's MapCollisionLoss on decoded plans [B,52,6] (descaled, sample-minor rows) -> (per-plan values [B],
         d total / d traj [B,52,6]); cld_map_collision_loss."""
-        traj = self._f32(traj)
-        B = traj.shape[0]
-        traj = self._f32(traj, (B, T, 6))
-        cc, keep = self._map_collision(cfg, B)
-        gi = None if grad_in is None else self._f32(grad_in, (B, T, 6))
-        loss = torch.empty(B, dtype=torch.float32, device=self.device)
-        grad = torch.empty(B, T, 6, dtype=torch.float32, device=self.device) if want_grad else None
-        with torch.cuda.device(self.device), self._map_source_term(cfg, B):
-            self._check(self.lib.cld_map_collision_loss(self._h, _ptr(traj), C.byref(cc), _ptr(gi), _ptr(loss), _ptr(grad), B, self._stream()),
-                        "cld_map_collision_loss")
+        loss, grad, _ = self._plan_loss("cld_map_collision_loss", self._map_collision, traj, cfg, grad_in, want_grad, terms={"map_collision": cfg})
         return (loss, grad) if want_grad else loss
 
     def agent_collision(self, traj, collision: Mapping, grad_in=None, want_grad=True):
         """Upstream's AgentCollisionLoss on decoded plans [B,52,6] (descaled, sample-minor rows) -> (per-agent values [B] as
         upstream files them under guide_losses, d total / d traj [B,52,6]); cld_agent_collision."""
-        traj = self._f32(traj)
-        B = traj.shape[0]
-        traj = self._f32(traj, (B, T, 6))
-        cc, keep = self._collision(collision, B)
-        gi = None if grad_in is None else self._f32(grad_in, (B, T, 6))
-        loss = torch.empty(B, dtype=torch.float32, device=self.device)
-        grad = torch.empty(B, T, 6, dtype=torch.float32, device=self.device) if want_grad else None
-        with torch.cuda.device(self.device):
-            self._check(self.lib.cld_agent_collision(self._h, _ptr(traj), C.byref(cc), _ptr(gi), _ptr(loss), _ptr(grad), B, self._stream()),
-                        "cld_agent_collision")
+        loss, grad, _ = self._plan_loss("cld_agent_collision", self._collision, traj, collision, grad_in, want_grad)
         return (loss, grad) if want_grad else loss
 
     def guidance_losses(self, traj, guidance: Mapping):
@@ -981,7 +878,7 @@ class Engine:
         xn = torch.empty_like(mean) if z is not None else None
         gr = torch.empty_like(mean) if want_grad else None
         ws, wsn = self._workspace(B)
-        with torch.cuda.device(self.device), self._goal_term(guidance, B), self._social_term(guidance, B), self._pair_term(guidance, B), self._lane_term(guidance, B), self._map_source_term((guidance or {}).get("map_collision"), B):
+        with torch.cuda.device(self.device), self._handle_terms(guidance, B):
             self._check(self.lib.cld_guidance_step(self._h, _ptr(mean), _ptr(cond), C.byref(cg), C.c_float(sigma), _ptr(z),
                                                    _ptr(mg), _ptr(xn), _ptr(gr), B, ws, wsn, self._stream()), "cld_guidance_step")
         out = (mg,) + ((xn,) if z is not None else ()) + ((gr,) if want_grad else ())
@@ -1044,7 +941,7 @@ class Engine:
         x1 = torch.empty_like(x_T) if (want_x1 and 1 in range(0, self.n_timesteps, self.stride)) else None
         logp = torch.empty(B, dtype=torch.float32, device=self.device) if want_logp else None
         cfg = non_cond is not None and guidance_w != 0.0
-        with torch.cuda.device(self.device), self._goal_term(guidance, B), self._social_term(guidance, B), self._pair_term(guidance, B), self._lane_term(guidance, B), self._map_source_term((guidance or {}).get("map_collision"), B):
+        with torch.cuda.device(self.device), self._handle_terms(guidance, B):
             if guidance is not None and guidance.get("reconstruction") is not None:
                 cg, keep = self._guidance(guidance, B)
                 rc, rkeep = self._recon(guidance["reconstruction"])
@@ -1092,7 +989,7 @@ class Engine:
         gr = torch.empty_like(x_t) if guided and want_grad else None
         ws, wsn = self._workspace(2 * ((B + 15) // 16 * 16) if cfg else B)
         sigma = C.c_float()
-        with torch.cuda.device(self.device), self._goal_term(guidance, B), self._social_term(guidance, B), self._pair_term(guidance, B), self._lane_term(guidance, B), self._map_source_term((guidance or {}).get("map_collision"), B):
+        with torch.cuda.device(self.device), self._handle_terms(guidance, B):
             self._check(self.lib.cld_sample_step(self._h, _ptr(x_t), _ptr(cond), _ptr(non_cond), C.c_float(guidance_w),
                                                  None if cg is None else C.byref(cg), int(t_idx), _ptr(z), _ptr(xn), _ptr(mean),
                                                  _ptr(mg), _ptr(gr), C.byref(sigma), B, ws, wsn, self._stream()), "cld_sample_step")
@@ -1163,7 +1060,7 @@ class Engine:
         x0h, gx, x0g = ((torch.empty_like(x_t) for _ in range(3)) if guided else (None, None, None))
         ws, wsn = self._recon_workspace(B, cfg)
         sigma = C.c_float()
-        with torch.cuda.device(self.device), self._goal_term(guidance, B), self._social_term(guidance, B), self._pair_term(guidance, B), self._lane_term(guidance, B), self._map_source_term((guidance or {}).get("map_collision"), B):
+        with torch.cuda.device(self.device), self._handle_terms(guidance, B):
             self._check(self.lib.cld_recon_step(self._h, _ptr(x_t), _ptr(cond), _ptr(non_cond), C.c_float(guidance_w), C.byref(cg),
                                                 C.byref(rc), int(t_idx), _ptr(z), _ptr(xn), _ptr(x0h), _ptr(gx), _ptr(x0g), _ptr(mean),
                                                 C.byref(sigma), B, C.c_uint64(seed), C.c_uint64(salt), ws, wsn, self._stream()),

@@ -78,7 +78,7 @@ def time_case(e, agents, g, rounds):
     if hasattr(e.lib, "cld_set_map_source"):
         term = dict(base, map_source=dict(maps=maps, scene_map=scene_map, map_from_world=mfw, world=world))
         cc_m, keep_m = e._map_collision(term, agents)
-        with e._map_source_term(term, agents):
+        with e._handle_terms({"map_collision": term}, agents):
             res["map"] = windows(lambda: call(cc_m), rounds)
         res["map_equals_raster"] = bool(torch.equal(loss, value_r) and torch.equal(grad, grad_r))
 

@@ -325,6 +325,92 @@ def test_the_lane_gradient_is_added_after_the_social_and_pair_terms(eng):
         assert not torch.equal(eng.guidance_step(mean, cond, {q: v for q, v in gd.items() if q != k}, sigma=0.0, want_grad=True)[1], grad)
 
 
+CHAIN = ("agent_collision", "map_collision", "goal", "social_group", "pair", "lane")
+
+
+def six_term_case(eng, N, steps=1):
+    """Nine agents x N samples with all six plan-space terms and a caller gradient -> (mean, cond, cs, guidance dict, the stand-alone
+    loss of every term by its guidance key, ext_grad).  The agent-collision scene puts the agents 3 m apart, the map term reads a
+    random 32 x 32 drivable raster at 2 px/m, goals / social group / pairs / lanes overlap on agents 1 .. 7."""
+    from tests.test_gpu_goal import engine_goal
+    from tests.test_gpu_pair import engine_term as pair_term
+    from tests.test_gpu_social import engine_term as social_term
+    A = 9
+    B = A * N
+    mean, cond, cs, term = guided_case(A, N, 81)
+    rng = np.random.default_rng(82)
+    i = np.arange(A)
+    W = np.zeros((A, 3, 3), np.float32)
+    W[:, 0, 0] = W[:, 1, 1] = W[:, 2, 2] = 1.0
+    W[:, 0, 2], W[:, 1, 2] = 6.0 * i, 2.0 * (i % 3)
+    Wd = torch.from_numpy(W).double()
+    F = Wd.clone()
+    F[:, :2, 2] = -Wd[:, :2, 2]
+    speed = cs[::N, 2].clone()
+    sc = synth.make_collision_scene([A], 83, spacing=3.0)
+    col = dict(extent=torch.from_numpy(sc["extent"]), world_from_agent=torch.from_numpy(sc["world_from_agent"]), curr_speed=speed,
+               scene_sizes=[A], weight=40.0, num_samp=N)
+    R = torch.zeros(A, 3, 3)
+    R[:, 0, 0] = R[:, 1, 1] = 2.0
+    R[:, 0, 2], R[:, 1, 2], R[:, 2, 2] = 6.0, 16.0, 1.0
+    mcol = dict(extent=torch.from_numpy(sc["extent"]), raster_from_agent=R, drivable_map=torch.from_numpy((rng.random((A, 32, 32)) < 0.6).astype(np.uint8)),
+                curr_speed=speed, weight=0.3, num_samp=N)
+    local = torch.tensor([[3.0, 2.5], [0.5, 12.0], [6.0, 1.0], [9.0, -2.0]] * 3, dtype=torch.float64)[:A]
+    goal = engine_goal(dict(kind=torch.tensor([1, 1, 2, 2] * 3, dtype=torch.int32)[:A], target_time=torch.tensor([0, 0, 34, 50] * 3, dtype=torch.int32)[:A],
+                            urgency=torch.tensor([0.5, 1.0, 0.5, 0.5] * 3, dtype=torch.float64)[:A], pref_speed=torch.full((A,), 1.42, dtype=torch.float64),
+                            scale=torch.full((A,), 0.4 / N, dtype=torch.float64), reached=torch.zeros(A, dtype=torch.bool), global_t=4, dt=0.1,
+                            min_progress_dist=0.5, target_pos=(local + Wd[:, :2, 2]).float().double(), agent_from_world=F), N)
+    pair = dict(target=[2, 4, 5], ref=[3, 2, 7], kind=["keep_distance", "stay_away", "front_collision"], lo=[20.0, 30.0, 0.0], hi=[25.0, 35.0, 0.0],
+                decay=[0.0, 0.9, 0.0], scale=[0.7 / N, 20.0 / N, 0.3 / N], world_from_agent=Wd, agent_from_world=None)
+    social = dict(groups=[[1, 2, 4, 5]], leader=[2], social_dist=[1.5], cohesion=[1.0], scale=[0.05 / N], world_from_agent=Wd)
+    r = torch.from_numpy((rng.integers(0, 1 << 30, (1, steps, B, 52)) % 3).astype(np.int32))
+    u = torch.from_numpy(rng.uniform(0.0, 0.999, (1, steps, B, 52)).astype(np.float32))
+    ext = torch.from_numpy(synth.normal(84, "six_term_ext_grad", (B, 52, 6))) * 0.05
+    te = engine_term(term, N)
+    gd = dict(curr_states=cs, agent_collision=col, map_collision=mcol, goal=goal, social_group=social_term(social, N, draw_r=r, draw_u=u),
+              pair=pair_term(pair, N), lane=te, ext_grad=ext, optimizer="sgd", lr=0.01, grad_steps=steps)
+    parts = {"agent_collision": (eng.agent_collision, col), "map_collision": (eng.map_collision, mcol), "goal": (eng.goal_loss, goal),
+             "social_group": (eng.social_group_loss, social_term(social, N, draw_r=r[0, 0], draw_u=u[0, 0])), "pair": (eng.pair_loss, gd["pair"]),
+             "lane": (eng.lane_loss, te)}
+    return mean, cond, cs, gd, parts, ext
+
+
+@pytest.mark.parametrize("N", [1, 2])
+def test_the_six_plan_space_terms_are_chained_in_order_on_top_of_the_callers_gradient(eng, N):
+    """All six plan-space terms and a caller ext_grad in one SGD step: the gradient has the bits of decode -> agent collision -> map
+    collision -> goal -> social group -> pair -> lane chained through grad_in in THAT order, starting from ext_grad -> VJP (the same
+    decode and loss kernels on the same inputs: no tolerance).  Swapping any two neighbours of the chain gives other bits, and so does
+    leaving out any term or the caller's gradient."""
+    mean, cond, cs, gd, parts, ext = six_term_case(eng, N)
+
+    def chain(order):
+        g = ext
+        traj = eng.decode(mean, cond, cs, descaled_output=True)
+        for k in order:
+            fn, te = parts[k]
+            g = fn(traj, te, grad_in=g)[1]
+        return eng.decode_vjp(mean, cond, cs, g)
+    _, grad = eng.guidance_step(mean, cond, gd, sigma=0.0, want_grad=True)
+    right = chain(CHAIN)
+    assert float(right.abs().max()) > 0 and torch.equal(grad, right)
+    for j in range(len(CHAIN) - 1):
+        order = list(CHAIN)
+        order[j], order[j + 1] = order[j + 1], order[j]
+        assert not torch.equal(chain(order), right), order
+    for k in CHAIN + ("ext_grad",):
+        assert not torch.equal(eng.guidance_step(mean, cond, {q: v for q, v in gd.items() if q != k}, sigma=0.0, want_grad=True)[1], grad), k
+
+
+def test_two_grad_steps_over_the_six_terms_give_the_same_bits_on_a_second_call(eng):
+    """grad_steps = 2 over the six-term chain (the second evaluation reads its own social draws): guided mean and gradient are
+    reproducible bit for bit, and the second step matters."""
+    mean, cond, cs, gd, _, _ = six_term_case(eng, 2, steps=2)
+    mg, grad = eng.guidance_step(mean, cond, gd, sigma=0.0, want_grad=True)
+    mg2, grad2 = eng.guidance_step(mean, cond, gd, sigma=0.0, want_grad=True)
+    assert torch.equal(mg, mg2) and torch.equal(grad, grad2)
+    assert not torch.equal(eng.guidance_step(mean, cond, dict(gd, grad_steps=1), sigma=0.0), mg)
+
+
 def test_adam_with_three_grad_steps_evaluates_the_lane_term_on_every_iterate(eng):
     """Adam, grad_steps = 3, step by step on the library's own iterates, as tests/test_gpu_pair.py does for the pair term: the iterate
     after k - 1 steps is what the call with grad_steps = k - 1 returns; the reference gradient of step k is taken THERE (decode, the
