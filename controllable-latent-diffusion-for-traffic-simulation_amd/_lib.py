@@ -1,4 +1,5 @@
-"""ctypes binding of libcld_hip.so (C-ABI: include/cld.h, include/cld_lane.h, include/cld_recon.h, include/cld_eval.h).
+"""ctypes binding of libcld_hip.so (C-ABI: include/cld.h, include/cld_lane.h, include/cld_recon.h, include/cld_solver.h,
+include/cld_eval.h).
 
 The product path has NO fallback: if the HIP library is missing or a call
 fails, a `CldError` is raised.  Nothing under `oracle/` is ever imported here.
@@ -311,6 +312,26 @@ RECON_SIGNATURES = {
     "cld_debug_recon_grid_cap": (C.c_int32, [C.c_int32]),
 }
 
+class CldSolver(C.Structure):
+    """include/cld_solver.h `cld_solver` (a few-step sampler: kind, K, a HOST pointer to K strictly decreasing timesteps, eta)."""
+    _fields_ = [("kind", C.c_int32), ("n_steps", C.c_int32), ("timesteps", C.c_void_p), ("eta", C.c_float)]
+
+
+SOLVER_KINDS = {"ddim": 0, "dpmpp_2m": 1}      # include/cld_solver.h CLD_SOLVER_*
+SOLVER_TABLE_COLS = ("a", "b", "c0", "c1", "sqrt_recip_acp", "sqrt_recipm1_acp", "sigma", "sigma_g")      # CLD_SOLVER_TABLE_COLS
+
+# name -> (restype, argtypes); every symbol include/cld_solver.h declares (a table of its own, as the lane table)
+SOLVER_SIGNATURES = {
+    "cld_solver_workspace_bytes": (C.c_size_t, [_P, C.c_int32, C.c_int32]),
+    "cld_solver_tables": (C.c_int, [_P, C.POINTER(CldSolver), _P]),
+    "cld_sample_solver": (C.c_int, [_P, C.POINTER(CldSolver), _P, _P, _P, _P, C.c_float, C.POINTER(CldGuidance), _P, C.c_int32, C.c_uint64,
+                                    _P, C.c_size_t, _P]),
+    "cld_solver_step": (C.c_int, [_P, C.POINTER(CldSolver), C.c_int32, _P, _P, _P, _P, _P, C.c_float, C.POINTER(CldGuidance), _P, _P, _P, _P, _P,
+                                  C.c_int32, C.c_uint64, _P, C.c_size_t, _P]),
+    "cld_debug_solver_grid_cap": (C.c_int32, [C.c_int32]),
+    "cld_debug_solver_kernel": (C.c_int, [_P, C.POINTER(CldSolver), C.c_int32, _P, _P, _P, C.c_float, _P, _P, _P, _P, _P, C.c_int32, C.c_uint64, _P]),
+}
+
 # name -> (restype, argtypes); every symbol include/cld_eval.h declares (the open-loop sample metrics; a third table of its own)
 EVAL_SIGNATURES = {
     "cld_sample_metrics_workspace_bytes": (C.c_size_t, [C.c_int32]),
@@ -342,7 +363,7 @@ def load():
     # library first would pull /opt/rocm's runtime in beside torch's and break device init.
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
-    for table in (SIGNATURES, LANE_SIGNATURES, RECON_SIGNATURES, EVAL_SIGNATURES):
+    for table in (SIGNATURES, LANE_SIGNATURES, RECON_SIGNATURES, SOLVER_SIGNATURES, EVAL_SIGNATURES):
         for name, (res, args) in table.items():
             fn = getattr(lib, name)      # AttributeError if the library does not export it
             fn.restype, fn.argtypes = res, args

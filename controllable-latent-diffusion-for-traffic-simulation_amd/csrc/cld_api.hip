@@ -14,10 +14,12 @@
 #include "../../include/cld_eval.h"
 #include "../../include/cld_lane.h"
 #include "../../include/cld_recon.h"
+#include "../../include/cld_solver.h"
 #include "cld_kernels.h"
 #include "lane_kernels.h"
 #include "recon_kernels.h"
 #include "sample_metrics_kernels.h"
+#include "solver_kernels.h"
 #include "train.h"
 
 using namespace cld;
@@ -72,6 +74,7 @@ struct cld_handle_s {
     // schedule (host, fp32 as in dm_model.py:29-56)
     std::vector<float> x_t_cof, noise_cof, plvc, sqrt_acp, sqrt_1m_acp, sqrt_recip_acp, sqrt_recipm1_acp;
     std::vector<float> post_coef1, post_coef2;       // posterior_mean_coef1 / 2 (dm_model.py:50-53; the reconstruction-guided step, cld_recon.h)
+    std::vector<float> acp;                          // alphas_cumprod itself (what the few-step samplers form their coefficients from, cld_solver.h)
     float* qs_tab = nullptr;            // device [2][n_timesteps]: sqrt(alphas_cumprod), sqrt(1 - alphas_cumprod) (q_sample, dm_model.py:91-96)
     // device-side model
     ResBlock blocks[12];
@@ -198,6 +201,7 @@ void build_schedule(cld_handle h) {
     // alphas - alphas_cumprod * alphas (noise_cof) then amplifies
     double run = 1.0;
     for (int i = 0; i < n; ++i) { run *= (double)alphas[i]; acp[i] = (float)run; acp_prev[i] = i ? acp[i - 1] : 1.0f; }
+    h->acp = acp;
     h->x_t_cof.resize(n); h->noise_cof.resize(n); h->plvc.resize(n); h->sqrt_acp.resize(n); h->sqrt_1m_acp.resize(n);
     h->sqrt_recip_acp.resize(n); h->sqrt_recipm1_acp.resize(n); h->post_coef1.resize(n); h->post_coef2.resize(n);
     for (int i = 0; i < n; ++i) {
@@ -2827,6 +2831,197 @@ int cld_sample_recon(cld_handle h, const float* x_T, const float* noise, const f
             if (logp) HIPCK(h, launch_logprob(w.xw, w.meanb, std::exp(0.5f * h->plvc[0]), logp, B, s));
         }
     }
+    return CLD_OK;
+}
+
+/* ---- few-step sampling (include/cld_solver.h; solver_kernels.hip) ---- */
+namespace {
+
+// what one step applies: the coefficients of cld_solver.h in double, rounded to fp32 once
+struct SolverCoef { float a, b, c0, c1, rc, rm1, sigma, sigma_g; int form; bool second; };
+
+int check_solver(cld_handle h, const char* fn, const cld_solver* sv) {
+    if (!h) return CLD_ERR_ARG;
+    if (!sv) return fail(h, CLD_ERR_ARG, std::string(fn) + ": null solver");
+    if (sv->kind != CLD_SOLVER_DDIM && sv->kind != CLD_SOLVER_DPMPP_2M) return fail(h, CLD_ERR_ARG, std::string(fn) + ": unknown solver kind (CLD_SOLVER_DDIM / CLD_SOLVER_DPMPP_2M)");
+    if (sv->n_steps < 1) return fail(h, CLD_ERR_ARG, std::string(fn) + ": n_steps < 1 (K >= 1 timesteps)");
+    if (!sv->timesteps) return fail(h, CLD_ERR_ARG, std::string(fn) + ": null timesteps");
+    for (int k = 0; k < sv->n_steps; ++k) {
+        if (sv->timesteps[k] < 0 || sv->timesteps[k] >= h->cfg.n_timesteps)
+            return fail(h, CLD_ERR_ARG, std::string(fn) + ": timestep out of range [0, n_timesteps) at index " + std::to_string(k));
+        if (k && sv->timesteps[k] >= sv->timesteps[k - 1])
+            return fail(h, CLD_ERR_ARG, std::string(fn) + ": timesteps not strictly decreasing at index " + std::to_string(k));
+    }
+    if (!(sv->eta >= 0.f && sv->eta <= 1.f)) return fail(h, CLD_ERR_ARG, std::string(fn) + ": eta outside [0, 1]");
+    if (sv->kind == CLD_SOLVER_DPMPP_2M && sv->eta != 0.f) return fail(h, CLD_ERR_ARG, std::string(fn) + ": DPM-Solver++(2M) is deterministic: eta != 0 is refused");
+    return CLD_OK;
+}
+
+SolverCoef solver_coef(cld_handle h, const cld_solver* sv, int k) {
+    const int K = sv->n_steps;
+    const bool last = k == K - 1;
+    auto acp = [&](int kk) { return kk >= K ? 1.0 : (double)h->acp[sv->timesteps[kk]]; };
+    auto lam = [&](int kk) { const double a = acp(kk); return 0.5 * std::log(a / (1.0 - a)); };     // finite for kk < K
+    const double as = acp(k), ap = acp(k + 1);
+    SolverCoef c{};
+    c.rc = (float)std::sqrt(1.0 / as);
+    c.rm1 = (float)std::sqrt(1.0 / as - 1.0);
+    const double jump = (1.0 - ap) / (1.0 - as) * (1.0 - as / ap);      // the DDPM posterior variance of the jump s -> p
+    c.sigma_g = (float)std::sqrt(std::max(jump, 1e-20));
+    c.c0 = 1.f; c.c1 = 0.f;
+    if (sv->kind == CLD_SOLVER_DDIM) {
+        const double var = (double)sv->eta * (double)sv->eta * jump;
+        c.sigma = last ? 0.f : (float)std::sqrt(var);
+        c.a = (float)std::sqrt(ap / as);
+        c.b = (float)(std::sqrt(std::max(1.0 - ap - var, 0.0)) - std::sqrt(ap * (1.0 - as) / as));
+        c.form = SOLVER_FORM_DDIM;
+    } else {
+        c.sigma = 0.f;
+        c.a = (float)std::sqrt((1.0 - ap) / (1.0 - as));
+        // -sqrt(acp_p) expm1(-h): the last step has lambda_p = +inf, expm1(-inf) = -1
+        c.b = last ? 1.f : (float)(-std::sqrt(ap) * std::expm1(-(lam(k + 1) - lam(k))));
+        c.second = k > 0 && !last;
+        if (c.second) {
+            const double r = (lam(k) - lam(k - 1)) / (lam(k + 1) - lam(k));
+            c.c0 = (float)(1.0 + 1.0 / (2.0 * r)); c.c1 = (float)(1.0 / (2.0 * r));
+        }
+        c.form = SOLVER_FORM_2M;
+    }
+    if (last) c.form = SOLVER_FORM_FINAL;
+    return c;
+}
+
+// the scalar arguments of the step kernel: coefficients, CFG weights, the generator's key
+SolverStepArgs solver_kernel_args(const SolverCoef& c, float guidance_w, int k, uint64_t seed, int B) {
+    SolverStepArgs q{};
+    q.w1 = (float)(1.0 + (double)guidance_w); q.nw = -guidance_w; q.rc = c.rc; q.nrm1 = -c.rm1;
+    q.a = c.a; q.b = c.b; q.c0 = c.c0; q.nc1 = -c.c1; q.sigma = c.sigma; q.form = c.form;
+    q.seed = seed; q.salt = (unsigned long long)k; q.rows = (long)B * T;
+    return q;
+}
+
+size_t solver_sampler_bytes(cld_handle h, int B, bool cfg) { return (cld_workspace_bytes(h, cfg ? 2 * pad16(B) : B) + 255) / 256 * 256; }
+
+int check_solver_call(cld_handle h, const char* fn, const cld_solver* sv, const cld_guidance* gd, int B, bool cfg, const void* ws, size_t ws_bytes) {
+    if (!h) return CLD_ERR_ARG;
+    int rc = check_solver(h, fn, sv);
+    if (rc) return rc;
+    if (B > (1 << 19)) return fail(h, CLD_ERR_ARG, std::string(fn) + ": B out of range [1, 2^19]");
+    if ((rc = check_common(h, fn, cfg ? 2 * pad16(B) : B, 0, ws, ws_bytes)) != CLD_OK) return rc;
+    if (ws_bytes < cld_solver_workspace_bytes(h, B, cfg)) return fail(h, CLD_ERR_WORKSPACE, std::string(fn) + ": workspace too small (cld_solver_workspace_bytes)");
+    if (gd) {
+        if (gd->guide_clean != 0) return fail(h, CLD_ERR_ARG, std::string(fn) + ": guide_clean != 0 is not built on the few-step path (mean-form guidance only)");
+        if ((rc = check_guidance(h, fn, gd, B, sv->n_steps)) != CLD_OK) return rc;
+    }
+    return CLD_OK;
+}
+
+// Step k on the latent in w.xw (CFG: rows [bp, 2 bp) hold the same latent, w.cb the conditional / unconditional bias rows): U-Net,
+// head (noise prediction only, both halves uncombined), the solver kernel, optional guidance step on its deterministic part.
+// Leaves x' in w.xw (both halves) and x0_hat in `hist` (when given; a second-order step reads the preceding one from it first).
+int solver_iteration(cld_handle h, const Ws& w, const cld_solver* sv, int k, bool cfg, int B, int bp, float* hist, const float* z, uint64_t seed,
+                     const float* cond, float guidance_w, const cld_guidance* gd, float* x0_hat, float* mu, float* mu_guided, float* grad,
+                     hipStream_t s) {
+    const int bpn = cfg ? 2 * bp : bp;
+    const size_t half = (size_t)bp * T * D;
+    const SolverCoef c = solver_coef(h, sv, k);
+    const bool last = k == sv->n_steps - 1;
+    const bool guide = gd && (last ? gd->apply_output != 0 : !gd->no_intermediate);
+    h->fuse_upd = nullptr;                               // the tail chain leaves the update to the kernel below
+    HIPCK(h, run_unet(h, w, w.xw, sv->timesteps[k], bpn, s));
+    HeadArgs a{};
+    head_source(h, w, a); a.w = h->head_w; a.b = h->head_b; a.x = w.xw; a.eps_out = w.xtmp; a.B = bpn; a.b_pad = bpn;
+    HIPCK(h, launch_head(a, s));
+    SolverStepArgs q = solver_kernel_args(c, guidance_w, k, seed, B);
+    q.x = w.xw; q.eps_c = w.xtmp; q.eps_u = cfg ? w.xtmp + half : nullptr;
+    q.x0_prev = c.second ? hist : nullptr; q.z = z; q.hist = hist;
+    q.x_out = guide ? nullptr : w.xw; q.x_out2 = (guide || !cfg) ? nullptr : w.xw + half; q.det_out = guide ? w.meanb : nullptr;
+    q.x0_out = x0_hat; q.mu_out = mu;
+    if (guide) q.sigma = 0.f;                            // the guidance kernel adds sigma_k z behind its step
+    HIPCK(h, launch_solver_step(q, s));
+    if (guide)
+        return run_guidance(h, w, gd, B, !last, c.sigma_g, c.sigma, w.meanb, cond, z, seed, (unsigned long long)k, mu_guided, w.xw,
+                            cfg ? w.xw + half : nullptr, grad, s);
+    return CLD_OK;
+}
+
+}  // namespace
+
+size_t cld_solver_workspace_bytes(cld_handle h, int32_t B, int32_t cfg) {
+    if (!h || B < 1 || B > (1 << 19)) return 0;
+    return solver_sampler_bytes(h, B, cfg != 0) + (size_t)B * T * D * sizeof(float);
+}
+
+int32_t cld_debug_solver_grid_cap(int32_t cap) { return solver_grid_cap(cap); }
+
+int cld_debug_solver_kernel(cld_handle h, const cld_solver* sv, int32_t k, const float* x, const float* eps_c, const float* eps_u, float guidance_w,
+                            const float* x0_prev, const float* z, float* x_next, float* x0_hat, float* mu, int32_t B, uint64_t seed, void* stream) {
+    int rc = check_solver(h, "cld_debug_solver_kernel", sv);
+    if (rc) return rc;
+    if (B < 1 || B > (1 << 19)) return fail(h, CLD_ERR_ARG, "cld_debug_solver_kernel: B out of range [1, 2^19]");
+    if (k < 0 || k >= sv->n_steps) return fail(h, CLD_ERR_ARG, "cld_debug_solver_kernel: step index out of range [0, n_steps)");
+    if (!x || !eps_c) return fail(h, CLD_ERR_ARG, "cld_debug_solver_kernel: null pointer");
+    const SolverCoef c = solver_coef(h, sv, k);
+    if (c.second && !x0_prev) return fail(h, CLD_ERR_ARG, "cld_debug_solver_kernel: a second-order step (2M, 0 < k < K-1) needs x0_prev");
+    if (misaligned({x, eps_c, eps_u, x0_prev, z, x_next, x0_hat, mu})) return fail(h, CLD_ERR_ARG, "cld_debug_solver_kernel: tensors must be 16-byte aligned");
+    SolverStepArgs q = solver_kernel_args(c, guidance_w, k, seed, B);
+    q.x = x; q.eps_c = eps_c; q.eps_u = eps_u; q.x0_prev = c.second ? x0_prev : nullptr; q.z = z;
+    q.x_out = x_next; q.x0_out = x0_hat; q.mu_out = mu;
+    HIPCK(h, launch_solver_step(q, static_cast<hipStream_t>(stream)));
+    return CLD_OK;
+}
+
+int cld_solver_tables(cld_handle h, const cld_solver* sv, float* table) {
+    int rc = check_solver(h, "cld_solver_tables", sv);
+    if (rc) return rc;
+    if (!table) return fail(h, CLD_ERR_ARG, "cld_solver_tables: null pointer");
+    for (int k = 0; k < sv->n_steps; ++k) {
+        const SolverCoef c = solver_coef(h, sv, k);
+        float* t = table + (size_t)k * CLD_SOLVER_TABLE_COLS;
+        t[0] = c.a; t[1] = c.b; t[2] = c.c0; t[3] = c.c1; t[4] = c.rc; t[5] = c.rm1; t[6] = c.sigma; t[7] = c.sigma_g;
+    }
+    return CLD_OK;
+}
+
+int cld_solver_step(cld_handle h, const cld_solver* sv, int32_t k, const float* x_t, float* x0_prev, const float* z, const float* cond,
+                    const float* non_cond, float guidance_w, const cld_guidance* gd, float* x_next, float* x0_hat, float* mu,
+                    float* mu_guided, float* grad, int32_t B, uint64_t seed, void* workspace, size_t workspace_bytes, void* stream) {
+    const bool cfg = non_cond != nullptr;
+    int rc = check_solver_call(h, "cld_solver_step", sv, gd, B, cfg, workspace, workspace_bytes);
+    if (rc) return rc;
+    if (!x_t || !cond) return fail(h, CLD_ERR_ARG, "cld_solver_step: null pointer");
+    if (k < 0 || k >= sv->n_steps) return fail(h, CLD_ERR_ARG, "cld_solver_step: step index out of range [0, n_steps)");
+    if (sv->kind == CLD_SOLVER_DPMPP_2M && k > 0 && k < sv->n_steps - 1 && !x0_prev)
+        return fail(h, CLD_ERR_ARG, "cld_solver_step: a second-order step (2M, 0 < k < K-1) needs x0_prev");
+    if (misaligned({x_t, x0_prev, z, x_next, x0_hat, mu, mu_guided, grad})) return fail(h, CLD_ERR_ARG, "cld_solver_step: tensors must be 16-byte aligned");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int bp = pad16(B);
+    Ws w = carve(workspace, cfg ? 2 * bp : bp);
+    if ((rc = load_inputs(h, w, B, bp, x_t, cond, non_cond, cfg, s)) != CLD_OK) return rc;
+    if ((rc = solver_iteration(h, w, sv, k, cfg, B, bp, x0_prev, z, seed, cond, guidance_w, gd, x0_hat, mu, mu_guided, grad, s)) != CLD_OK) return rc;
+    if (x_next) HIPCK(h, launch_unpack(w.xw, x_next, B, s));
+    return CLD_OK;
+}
+
+int cld_sample_solver(cld_handle h, const cld_solver* sv, const float* x_T, const float* noise, const float* cond, const float* non_cond,
+                      float guidance_w, const cld_guidance* gd, float* x0, int32_t B, uint64_t seed, void* workspace, size_t workspace_bytes,
+                      void* stream) {
+    const bool cfg = non_cond != nullptr;
+    int rc = check_solver_call(h, "cld_sample_solver", sv, gd, B, cfg, workspace, workspace_bytes);
+    if (rc) return rc;
+    if (!x_T || !cond) return fail(h, CLD_ERR_ARG, "cld_sample_solver: null pointer");
+    if (misaligned({x_T, noise, x0})) return fail(h, CLD_ERR_ARG, "cld_sample_solver: tensors must be 16-byte aligned");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int bp = pad16(B);
+    Ws w = carve(workspace, cfg ? 2 * bp : bp);
+    float* hist = reinterpret_cast<float*>(static_cast<char*>(workspace) + solver_sampler_bytes(h, B, cfg));
+    if ((rc = load_inputs(h, w, B, bp, x_T, cond, non_cond, cfg, s)) != CLD_OK) return rc;
+    for (int k = 0; k < sv->n_steps; ++k) {
+        rc = solver_iteration(h, w, sv, k, cfg, B, bp, hist, noise ? noise + (size_t)k * B * T * D : nullptr, seed, cond, guidance_w, gd, nullptr,
+                              nullptr, nullptr, nullptr, s);
+        if (rc) return rc;
+    }
+    if (x0) HIPCK(h, launch_unpack(w.xw, x0, B, s));
     return CLD_OK;
 }
 

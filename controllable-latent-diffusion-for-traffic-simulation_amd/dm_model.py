@@ -16,7 +16,7 @@ from typing import Mapping, Optional
 
 import torch
 
-from .engine import Engine
+from .engine import Engine, parse_sampler, refuse_sampler_guidance, solver_timesteps  # noqa: F401  (solver_timesteps: part of this module's surface)
 from ._lib import CldError
 
 
@@ -137,11 +137,15 @@ class DmModel:
     # ---- dm_model.py:98-142 ------------------------------------------------------------
     @torch.no_grad()
     def forward(self, data_batch, aux_info, algo_config, noise: Optional[Mapping] = None, seed: int = 0,
-                class_free_guide_w: float = 0.0, guidance: Optional[Mapping] = None, guidance_fn=None, **guidance_opt):
+                class_free_guide_w: float = 0.0, guidance: Optional[Mapping] = None, guidance_fn=None, sampler: Optional[Mapping] = None,
+                **guidance_opt):
         """`guidance_fn(traj [BN,52,6]) -> scalar` is a caller-defined torch loss on the decoded trajectories (e.g. one of
         upstream's guidance losses); it takes the place of the built-in losses (`guidance=`) through `Engine.sample_with_loss`
-        (`guidance_opt`: lr / optimizer / perturb_th).  Needs `noise=` and aux_info['curr_states']."""
+        (`guidance_opt`: lr / optimizer / perturb_th).  Needs `noise=` and aux_info['curr_states'].
+        `sampler`: a few-step sampler (see `sample_traj`); the reference has no counterpart of it."""
         if guidance_fn is not None:
+            if sampler is not None:
+                raise NotImplementedError("sampler= together with guidance_fn= is not built: the few-step samplers run the built-in guidance terms")
             num_samp = int(cfg_get(algo_config, "num_samp", 1))
             aux = repeat_by_expand_at(aux_info, repeats=num_samp, dim=0)
             if noise is None:
@@ -150,16 +154,23 @@ class DmModel:
             x0, x1 = self.engine.sample_with_loss(noise["x_T"], aux["cond_feat"], aux["curr_states"], noise["noise"], guidance_fn, **guidance_opt)
             return {"pred_traj": x0, "x1": x1, "log_prob_final": None, "aux_info": aux}
         return self.sample_traj(data_batch, algo_config, aux_info, noise=noise, seed=seed,
-                                class_free_guide_w=class_free_guide_w, guidance=guidance)
+                                class_free_guide_w=class_free_guide_w, guidance=guidance, sampler=sampler)
 
     def sample_traj(self, data_batch, algo_config, aux_info, noise: Optional[Mapping] = None, seed: int = 0,
-                    class_free_guide_w: float = 0.0, guidance: Optional[Mapping] = None):
+                    class_free_guide_w: float = 0.0, guidance: Optional[Mapping] = None, sampler: Optional[Mapping] = None):
         """`class_free_guide_w` != 0 needs aux_info['non_cond_feat'] and follows the upstream CFG definition
         (src/tbsim/models/diffuser.py:766-789; kwarg name as injected by policies/wrappers.py:143-167).
         `guidance` = dict(target_speed [B,52], loss_scale [B] | None, lr, perturb_th, optimizer): sampling-time guidance
         of every step's posterior mean (upstream diffuser.py:844-929; Engine._guidance); curr_states come from aux_info.  A
         `reconstruction` entry (Engine._recon: params, lr, perturb_th, descend) is passed through as it is and selects upstream's
-        guide_clean="video_diff" (include/cld_recon.h)."""
+        guide_clean="video_diff" (include/cld_recon.h).
+        `sampler` = {"kind": "ddim" | "dpmpp_2m", "steps": K or "timesteps": [...], "eta": float}: few-step sampling on a timestep subset
+        (include/cld_solver.h; Engine.sample_solver) instead of the ancestral loop.  `noise["noise"]` is then [K,BN,52,4] (read by DDIM
+        with eta > 0 only); the result has x1 = None and log_prob_final = None: step 1 and a final Gaussian do not exist on this
+        path.  None: the ancestral sampler, exactly as before."""
+        if sampler is not None:
+            refuse_sampler_guidance(guidance)
+            spec = parse_sampler(sampler, self.n_timesteps)
         batch_size = data_batch["history_positions"].size()[0]
         num_samp = int(cfg_get(algo_config, "num_samp", 1))
         BN = batch_size * num_samp
@@ -168,7 +179,8 @@ class DmModel:
             x_T, z = noise["x_T"], noise.get("noise")
         else:   # same draw count as the reference (one for x_T, one per step), from torch's device generator
             x_T = torch.randn(BN, 52, 4, device=self.device)
-            z = torch.randn(self.engine.loop_steps, BN, 52, 4, device=self.device)
+            draws = self.engine.loop_steps if sampler is None else (len(spec[1]) if spec[2] != 0.0 else 0)
+            z = torch.randn(draws, BN, 52, 4, device=self.device) if draws else None
         x_T = torch.as_tensor(x_T).reshape(BN, 52, 4)
         if guidance is not None:
             guidance = repeat_guidance(guidance, num_samp, aux_info["curr_states"])
@@ -177,6 +189,11 @@ class DmModel:
             # (`include_class_free_cond=True`, Engine.non_cond_feat).  Running unguided instead would be a silent wrong answer.
             raise CldError("class_free_guide_w != 0 needs aux_info['non_cond_feat'] [B,256] (ContextEncoder(..., include_class_free_cond=True) "
                            "or Engine.non_cond_feat(curr_states) produce it)")
+        if sampler is not None:
+            x0 = self.engine.sample_solver(x_T, aux_info["cond_feat"], sampler, noise=z, seed=seed,
+                                           non_cond=aux_info.get("non_cond_feat") if class_free_guide_w else None,
+                                           guidance_w=class_free_guide_w, guidance=guidance)
+            return {"pred_traj": x0, "x1": None, "log_prob_final": None, "aux_info": aux_info}
         x0, x1, logp = self.engine.sample(x_T, aux_info["cond_feat"], noise=z, seed=seed,
                                           non_cond=aux_info.get("non_cond_feat") if class_free_guide_w else None,
                                           guidance_w=class_free_guide_w, guidance=guidance)

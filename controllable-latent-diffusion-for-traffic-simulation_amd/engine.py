@@ -67,6 +67,57 @@ def pair_incidences(target, ref, A: int):
     return ids, start, inc
 
 
+def solver_timesteps(n_timesteps: int, K: int):
+    """The timestep subset of a K-step sampler: the unique values of rint(linspace(n_timesteps - 1, 0, K)), descending
+    (n = 100, K = 10: 99, 88, ..., 11, 0)."""
+    n_timesteps, K = int(n_timesteps), int(K)
+    if n_timesteps < 1 or K < 1:
+        raise CldError(f"solver_timesteps: n_timesteps = {n_timesteps} and K = {K} must be >= 1")
+    ts = np.unique(np.rint(np.linspace(n_timesteps - 1, 0, K)).astype(np.int64))[::-1]
+    return [int(t) for t in ts]
+
+
+def parse_sampler(sampler: Mapping, n_timesteps: int):
+    """A `sampler=` mapping {"kind": "ddim" | "dpmpp_2m", "steps": K or "timesteps": [...], "eta": float} -> (kind name, timesteps as a
+    contiguous int32 array, eta), refused with a CldError naming the cause as include/cld_solver.h refuses it.  Needs no device."""
+    if not isinstance(sampler, Mapping):
+        raise CldError("sampler: expected a mapping {'kind', 'steps' | 'timesteps', 'eta'}")
+    unknown = set(sampler) - {"kind", "steps", "timesteps", "eta"}
+    if unknown:
+        raise CldError(f"sampler: unknown keys {sorted(unknown)}")
+    kind = sampler.get("kind")
+    if kind not in _lib.SOLVER_KINDS:
+        raise CldError(f"sampler: unknown kind '{kind}' (one of {sorted(_lib.SOLVER_KINDS)})")
+    if (sampler.get("steps") is None) == (sampler.get("timesteps") is None):
+        raise CldError("sampler: give exactly one of 'steps' (K) and 'timesteps' (a strictly decreasing list)")
+    if sampler.get("steps") is not None:
+        if int(sampler["steps"]) < 1:
+            raise CldError("sampler: steps < 1 (K >= 1 timesteps)")
+        ts = solver_timesteps(n_timesteps, int(sampler["steps"]))
+    else:
+        ts = [int(t) for t in sampler["timesteps"]]
+    if len(ts) < 1:
+        raise CldError("sampler: n_steps < 1 (K >= 1 timesteps)")
+    for k, t in enumerate(ts):
+        if not 0 <= t < n_timesteps:
+            raise CldError(f"sampler: timestep out of range [0, n_timesteps) at index {k}")
+        if k and t >= ts[k - 1]:
+            raise CldError(f"sampler: timesteps not strictly decreasing at index {k}")
+    eta = float(sampler.get("eta", 0.0) or 0.0)
+    if not 0.0 <= eta <= 1.0:
+        raise CldError("sampler: eta outside [0, 1]")
+    if kind == "dpmpp_2m" and eta != 0.0:
+        raise CldError("sampler: DPM-Solver++(2M) is deterministic: eta != 0 is refused")
+    return kind, np.ascontiguousarray(ts, dtype=np.int32), eta
+
+
+def refuse_sampler_guidance(guidance: Optional[Mapping]) -> None:
+    """guide_clean / reconstruction guidance do not exist on the few-step path (include/cld_solver.h)."""
+    if guidance is not None and (guidance.get("guide_clean") or guidance.get("reconstruction") is not None):
+        which = "reconstruction (guide_clean=\"video_diff\")" if guidance.get("reconstruction") is not None or guidance.get("guide_clean") == "video_diff" else "guide_clean=True"
+        raise NotImplementedError(f"sampler= together with {which} guidance is not built: the few-step samplers guide the mean form only")
+
+
 def _param_table(lib, h, model):
     lib = lib or _lib.load()
     count, info, floats = (getattr(lib, f"cld_{model}_param_{s}") for s in ("count", "info", "floats"))
@@ -146,7 +197,7 @@ class Engine:
             rc = self.lib.cld_create(C.byref(cfg), C.byref(self._h))
         if rc != 0:
             raise CldError(f"cld_create failed ({rc})")
-        self._ws = self._ctx_ws = self._tws = self._vws = self._rws = self._recon_ws = None      # grow-only device scratch (_scratch): sampling, ContextEncoder,
+        self._ws = self._ctx_ws = self._tws = self._vws = self._rws = self._recon_ws = self._solver_ws = None      # grow-only device scratch (_scratch): sampling, ContextEncoder,
                                                                                 # U-Net training, VAE training, sort / Wasserstein,
                                                                                 # reconstruction guidance
         self._nc_map_feat = {}
@@ -1068,6 +1119,102 @@ class Engine:
         out = {"x_next": xn, "mean": mean, "sigma": float(sigma.value)}
         if guided:
             out.update(x0_hat=x0h, grad_xt=gx, x0_guided=x0g)
+        return out
+
+    # ------------------------------------------------------------------ few-step sampling (include/cld_solver.h)
+    def _solver(self, sampler: Mapping):
+        """`sampler=` mapping (parse_sampler) -> (CldSolver, the int32 array it points into, kept alive)."""
+        kind, ts, eta = parse_sampler(sampler, self.n_timesteps)
+        return _lib.CldSolver(_lib.SOLVER_KINDS[kind], len(ts), ts.ctypes.data, eta), ts
+
+    def _solver_workspace(self, B: int, cfg: bool):
+        return self._scratch("_solver_ws", int(self.lib.cld_solver_workspace_bytes(self._h, B, int(cfg))))
+
+    def solver_grid_cap(self, cap: int = 0) -> int:
+        """Tests only (cld_debug_solver_grid_cap): the most workgroups the solver step kernel takes; cap < 1 restores the default."""
+        return int(self.lib.cld_debug_solver_grid_cap(int(cap)))
+
+    def debug_solver_kernel(self, sampler: Mapping, k: int, x, eps, eps_uncond=None, guidance_w: float = 0.0, x0_prev=None, z=None, seed: int = 0):
+        """Tests only (cld_debug_solver_kernel): the step kernel alone on a given noise prediction -> dict(x_next, x0_hat, mu)."""
+        sv, ts = self._solver(sampler)
+        x = self._f32(x)
+        B = x.shape[0]
+        x, eps = self._f32(x, (B, T, D)), self._f32(eps, (B, T, D))
+        eu, prev, z = (None if v is None else self._f32(v, (B, T, D)) for v in (eps_uncond, x0_prev, z))
+        xn, x0h, mu = (torch.empty_like(x) for _ in range(3))
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cld_debug_solver_kernel(self._h, C.byref(sv), int(k), _ptr(x), _ptr(eps), _ptr(eu), C.c_float(guidance_w), _ptr(prev),
+                                                         _ptr(z), _ptr(xn), _ptr(x0h), _ptr(mu), B, C.c_uint64(seed), self._stream()),
+                        "cld_debug_solver_kernel")
+        return {"x_next": xn, "x0_hat": x0h, "mu": mu}
+
+    def solver_tables(self, sampler: Mapping) -> dict:
+        """The fp32 per-step coefficients the library applies (cld_solver_tables): dict(timesteps, a, b, c0, c1, sqrt_recip_acp,
+        sqrt_recipm1_acp, sigma, sigma_g), float32 [K] each."""
+        sv, ts = self._solver(sampler)
+        tab = np.empty((len(ts), len(_lib.SOLVER_TABLE_COLS)), np.float32)
+        self._check(self.lib.cld_solver_tables(self._h, C.byref(sv), tab.ctypes.data), "cld_solver_tables")
+        out = {name: tab[:, i].copy() for i, name in enumerate(_lib.SOLVER_TABLE_COLS)}
+        out["timesteps"] = ts.copy()
+        return out
+
+    def sample_solver(self, x_T, cond, sampler: Mapping, noise=None, seed: int = 0, non_cond=None, guidance_w: float = 0.0,
+                      guidance: Optional[Mapping] = None):
+        """The few-step loop (cld_sample_solver): DDIM(eta) or DPM-Solver++(2M) on the sampler's K timesteps -> x0 [B,52,4].  noise
+        [K,B,52,4] or None (the device generator, the draws of `sample`'s iteration k); eta = 0 and 2M draw nothing.  CFG and
+        `guidance` (mean form; see `_guidance`) as in `sample`.  The reference has no counterpart of this mode."""
+        refuse_sampler_guidance(guidance)
+        sv, ts = self._solver(sampler)
+        x_T = self._f32(x_T)
+        B = x_T.shape[0]
+        x_T = self._f32(x_T, (B, T, D)); cond = self._f32(cond, (B, COND))
+        noise = None if noise is None else self._f32(noise, (len(ts), B, T, D))
+        cfg = non_cond is not None and guidance_w != 0.0
+        non_cond = self._f32(non_cond, (B, COND)) if cfg else None
+        x0 = torch.empty_like(x_T)
+        with torch.cuda.device(self.device), self._handle_terms(guidance, B):
+            cg = keep = None
+            if guidance is not None:
+                cg, keep = self._guidance(guidance, B)
+            ws, wsn = self._solver_workspace(B, cfg)
+            self._check(self.lib.cld_sample_solver(self._h, C.byref(sv), _ptr(x_T), _ptr(noise), _ptr(cond), _ptr(non_cond), C.c_float(guidance_w),
+                                                   None if cg is None else C.byref(cg), _ptr(x0), B, C.c_uint64(seed), ws, wsn, self._stream()),
+                        "cld_sample_solver")
+        return x0
+
+    def solver_step(self, x_t, cond, sampler: Mapping, k: int, x0_prev=None, z=None, non_cond=None, guidance_w: float = 0.0,
+                    guidance: Optional[Mapping] = None, seed: int = 0, want_grad: bool = False):
+        """Step k of `sample_solver` on a given x_t (cld_solver_step) -> dict(x_next, x0_hat, mu [the deterministic part before
+        guidance], x0_prev [this step's x0_hat: what the next step takes], and on a guided step mu_guided [, grad]).  x0_prev: the
+        preceding step's clean prediction, needed by a second-order step (2M, 0 < k < K-1); it is not modified.  z None: the step's
+        noise is drawn on the device for (seed, k)."""
+        refuse_sampler_guidance(guidance)
+        sv, ts = self._solver(sampler)
+        x_t = self._f32(x_t)
+        B = x_t.shape[0]
+        x_t = self._f32(x_t, (B, T, D)); cond = self._f32(cond, (B, COND))
+        z = None if z is None else self._f32(z, (B, T, D))
+        hist = None if x0_prev is None else self._f32(x0_prev, (B, T, D)).clone()
+        cfg = non_cond is not None and guidance_w != 0.0
+        non_cond = self._f32(non_cond, (B, COND)) if cfg else None
+        last = int(k) == len(ts) - 1
+        guided = guidance is not None and (bool(guidance.get("output")) if last else bool(guidance.get("intermediate", True)))
+        xn, x0h, mu = (torch.empty_like(x_t) for _ in range(3))
+        mg = torch.empty_like(x_t) if guided else None
+        gr = torch.empty_like(x_t) if guided and want_grad else None
+        with torch.cuda.device(self.device), self._handle_terms(guidance, B):
+            cg = keep = None
+            if guidance is not None:
+                cg, keep = self._guidance(guidance, B)
+            ws, wsn = self._solver_workspace(B, cfg)
+            self._check(self.lib.cld_solver_step(self._h, C.byref(sv), int(k), _ptr(x_t), _ptr(hist), _ptr(z), _ptr(cond), _ptr(non_cond),
+                                                 C.c_float(guidance_w), None if cg is None else C.byref(cg), _ptr(xn), _ptr(x0h), _ptr(mu),
+                                                 _ptr(mg), _ptr(gr), B, C.c_uint64(seed), ws, wsn, self._stream()), "cld_solver_step")
+        out = {"x_next": xn, "x0_hat": x0h, "mu": mu, "x0_prev": x0h if hist is None else hist}
+        if guided:
+            out["mu_guided"] = mg
+            if want_grad:
+                out["grad"] = gr
         return out
 
     # ------------------------------------------------------------------ training (exact fp32; cld_unet_train_forward / cld_unet_backward)

@@ -24,7 +24,7 @@ import torch
 from . import _lib
 from ._lib import CldError
 from .dm_model import DmModel, repeat_guidance
-from .engine import raster_frames      # noqa: F401  (re-exported: the frames a map_source implies)
+from .engine import parse_sampler, raster_frames      # noqa: F401  (raster_frames re-exported: the frames a map_source implies)
 from .vae_model import VaeModel
 
 
@@ -422,7 +422,8 @@ class CldPolicy:
     @torch.no_grad()
     def get_action(self, obs_dict: Mapping, num_action_samples: int = 1, class_free_guide_w: float = 0.0,
                    guide_as_filter_only: bool = False, guide_with_gt: bool = False, guide_clean=False,
-                   step_index: int = 0, noise: Optional[Mapping] = None, guidance: Optional[Mapping] = None, plan=None, **kwargs):
+                   step_index: int = 0, noise: Optional[Mapping] = None, guidance: Optional[Mapping] = None, plan=None,
+                   sampler: Optional[Mapping] = None, **kwargs):
         """`DiffuserTrafficModel.get_action` (src/tbsim/algos/algos.py:2024-2099).  With guidance active (`set_guidance` or
         `guidance=`) the guidance losses of every sample are evaluated on the final output (diffuser.py:924-926), returned as
         info['guide_losses'], and the executed sample is the one `choose_action_from_guidance` picks (algos.py:2057-2064);
@@ -434,7 +435,12 @@ class CldPolicy:
         guidance_loss.py:930-1135) reads obs_dict['agent_from_world'] and / or ['world_from_agent'] [B,3,3] (one is computed from the
         other; ValueError without both) and, with a target_tolerance, obs_dict['agent_hist'] [B,Th,>=2]; `step_index` is its global_t
         (algos.py:2048); the arrival flags persist on the policy (`goal_reached`) and come back as info['goal_reached'].
+        `sampler`: a few-step sampler for the plan (DmModel.sample_traj; include/cld_solver.h) -- sample selection, the guidance losses on
+        the output, goal carry and follow_observation work as on the ancestral path; together with `guide_clean` it raises.
         Not built: `plan` -- it raises instead of being ignored."""
+        if sampler is not None and guide_clean:
+            raise NotImplementedError(f"sampler= together with guide_clean={guide_clean!r} is not built: the few-step samplers guide the mean form only")
+        loop_steps = self.vae.engine.loop_steps if sampler is None else len(parse_sampler(sampler, self.dm.n_timesteps)[1])
         video_diff = isinstance(guide_clean, str) and guide_clean == "video_diff"
         if video_diff and self._reconstruction is None:
             raise NotImplementedError("guide_clean='video_diff' needs CldPolicy.enable_reconstruction_guidance() first: the mode keeps a "
@@ -469,13 +475,13 @@ class CldPolicy:
             # the plan's loop iterations take evaluation indices social_iter .. social_iter + loop_steps - 1, the values reported on the
             # final output (below) the one behind them
             g = dict(g, social_group=dict(g["social_group"], iter_base=self.social_iter))
-            self.social_iter += eng.loop_steps + 1
+            self.social_iter += loop_steps + 1
         if g is not None and g.get("goal") is not None:
             carry = guidance is None
             g = dict(g, goal=self._goal_for_step(g["goal"], obs_dict, step_index, carry))
         out = self.dm({"history_positions": cond}, {k: aux[k] for k in ("cond_feat", "curr_states", "non_cond_feat") if k in aux},
                       {"num_samp": N}, noise=noise, class_free_guide_w=class_free_guide_w,
-                      guidance=None if guide_as_filter_only else g)
+                      guidance=None if guide_as_filter_only else g, **({} if sampler is None else {"sampler": sampler}))
         a = out["aux_info"]
         traj = eng.decode(out["pred_traj"], a["cond_feat"], a["curr_states"], descaled_output=True).reshape(B, N, 52, 6)
         pos, yaw = traj[..., :2].clone(), traj[..., 3:4].clone()
@@ -487,7 +493,7 @@ class CldPolicy:
             g_rep = repeat_guidance({k: v for k, v in g.items() if k != "curr_states"}, N, a["curr_states"])
             if g_rep.get("social_group") is not None:
                 sg = g_rep["social_group"]
-                g_rep["social_group"] = dict(sg, iter_base=int(sg.get("iter_base", 0)) + eng.loop_steps)
+                g_rep["social_group"] = dict(sg, iter_base=int(sg.get("iter_base", 0)) + loop_steps)
             losses, names = self._guide_losses(traj, g_rep, B, N, from_cfg)
             scene_of_agent = None
             if self.select_per_scene and from_cfg:
@@ -511,7 +517,8 @@ class CldPolicy:
 
 
 def closed_loop_rollout(policy: CldPolicy, cond_fn: Callable, centroid, yaw, curr_states, n_sim_steps: int,
-                        n_step_action: int = 5, gather: Optional[Callable] = None, timers=None, metrics=None, **get_action_kwargs):
+                        n_step_action: int = 5, gather: Optional[Callable] = None, timers=None, metrics=None, sampler: Optional[Mapping] = None,
+                        **get_action_kwargs):
     """The loop of `rollout_episodes` (`src/tbsim/utils/env_utils.py:255-304`) kept on the device:
     obs -> get_action -> take `n_step_action` steps of the plan -> new world pose -> re-plan.
     `cond_fn(step, world [B,3], curr_states [B,4], plans) -> cond_feat [B,256]` stands in for the observation +
@@ -534,8 +541,11 @@ def closed_loop_rollout(policy: CldPolicy, cond_fn: Callable, centroid, yaw, cur
     With collision guidance that follows the observation (`set_guidance(..., follow_observation=True)`) the same holds for
     `world_from_agent` (from the world pose; a social-group, pair or lane term reads it too), `curr_speed` (`curr_states[:, 2]`) and `world`
     [B,3], the pose itself, which a map_collision term in map mode is evaluated at; a raster-mode term needs `drivable_map` from `cond_fn` (SceneObserver gives it).
+    `sampler`: a few-step sampler every re-plan runs with (get_action's `sampler=`); None: the ancestral sampler.
     Returns the world poses after each sim step [n_sim_steps, B, 3]."""
     import inspect
+    if sampler is not None:
+        get_action_kwargs = dict(get_action_kwargs, sampler=sampler)
     from contextlib import nullcontext
     tm = (lambda k: timers.timed(k)) if timers is not None else (lambda k: nullcontext())
     eng = policy.vae.engine
