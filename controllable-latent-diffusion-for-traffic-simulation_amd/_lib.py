@@ -34,14 +34,14 @@ OPTIMIZERS = {"adam": 0, "sgd": 1}
 RES_FOLD = {"fused": 0, "separate": 1}      # cld_debug_res_fold (include/cld.h CLD_RES_FOLD_*)
 KERNELS = {"guide": 0, "decode": 1, "encode": 2, "unet": 3, "context": 4, "conv5": 5}        # cld_debug_force_kernel
 # cld_debug_force_kernel: the formulations each kernel has (include/cld.h CLD_FORM_*).  The numbers are reused across kernels (3 is "quad"
-# for the guide kernel, "chain1" for the U-Net, "winograd_f2" for the ContextEncoder and "winograd_whole" for the k5 layers), so a form
+# for the guide kernel, "chain1" for the U-Net and "winograd_whole" for the k5 layers), so a form
 # is named together with its kernel: form_id() refuses a name the kernel does not have.
 KERNEL_FORMS = {
     "guide": {"auto": 0, "valu": 1, "mfma": 2, "quad": 3},
     "decode": {"auto": 0, "valu": 1, "mfma": 2},
     "encode": {"auto": 0, "valu": 1, "mfma": 2},
     "unet": {"auto": 0, "layers": 1, "chain": 2, "chain1": 3, "chain4": 4, "chainw": 5, "chainw2": 6, "chainw1": 7},      # one launch per layer / LDS-resident layer chains
-    "context": {"auto": 0, "direct": 1, "winograd": 2, "winograd_f2": 3},       # the 3x3 / stride-1 convolutions of the ResNet-18
+    "context": {"auto": 0, "direct": 1, "winograd": 2},       # the 3x3 / stride-1 convolutions of the ResNet-18
     "conv5": {"auto": 0, "direct": 1, "winograd": 2, "winograd_whole": 3, "winograd_ksplit": 4},     # the k5 layers of the U-Net's L = 13 / 26 levels
 }
 FORMS = {name: v for forms in KERNEL_FORMS.values() for name, v in forms.items()}      # every name -> its number (the union of the above)

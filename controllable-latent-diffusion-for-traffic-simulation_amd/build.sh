@@ -12,7 +12,7 @@ FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC ${CLD_EXTRA_FLAGS:-} $*"
 TAG=$(echo "$FLAGS" | md5sum | cut -c1-8)
 OBJ=build/obj_$TAG
 mkdir -p "$OBJ"
-SRCS="conv_block conv_chain chain_wino misc_kernels context_kernels wino_kernels wino44_kernels wino1d_kernels wino1d_edge guide_kernels collision_kernels goal_kernels social_kernels pair_kernels lane_kernels recon_kernels solver_kernels sample_metrics_kernels raster_kernels metrics_kernels guide_metrics_kernels occupancy_kernels realism_kernels train_kernels vae_train_kernels cld_api"
+SRCS="conv_block conv_chain chain_wino misc_kernels context_kernels wino44_kernels wino1d_kernels wino1d_edge guide_kernels collision_kernels goal_kernels social_kernels pair_kernels lane_kernels recon_kernels solver_kernels sample_metrics_kernels raster_kernels metrics_kernels guide_metrics_kernels occupancy_kernels realism_kernels train_kernels vae_train_kernels cld_api"
 pids=()
 for s in $SRCS; do
     src=csrc/$s.hip

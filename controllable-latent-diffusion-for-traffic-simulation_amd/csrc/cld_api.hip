@@ -88,7 +88,7 @@ struct cld_handle_s {
     EncoderWeights enc{};
     bool has_encoder = false;
     // ContextEncoder (optional): stem, 19 NHWC convolutions, head
-    struct Conv2dLayer { float *wfrag = nullptr, *ufrag = nullptr, *ufrag44 = nullptr, *scale = nullptr, *shift = nullptr; int kh = 3, stride = 1, hin = 56, cin = 64, cout = 64; };   // ufrag: the Winograd-domain filters of a 3x3 / stride-1 layer (wino_kernels.hip)
+    struct Conv2dLayer { float *wfrag = nullptr, *ufrag44 = nullptr, *scale = nullptr, *shift = nullptr; int kh = 3, stride = 1, hin = 56, cin = 64, cout = 64; };   // ufrag44: the Winograd-domain filters of a 3x3 / stride-1 layer (wino44_kernels.hip)
     bool has_context = false;
     float *stem_w = nullptr, *stem_scale = nullptr, *stem_shift = nullptr;
     Conv2dLayer rn_conv[4][2][2], rn_ds[4];
@@ -850,7 +850,7 @@ int cld_debug_lds_floor(cld_handle h, size_t bytes) {
 }
 
 int cld_debug_force_kernel(cld_handle h, int32_t which, int32_t form) {
-    if (!h || which < 0 || which > 5 || form < 0 || form > (which == CLD_KERNEL_GUIDE || which == CLD_KERNEL_CONTEXT ? 3 : which == CLD_KERNEL_CONV5 ? 4 : (which == CLD_KERNEL_UNET ? 7 : 2))) return fail(h, CLD_ERR_ARG, "cld_debug_force_kernel: bad argument");
+    if (!h || which < 0 || which > 5 || form < 0 || form > (which == CLD_KERNEL_GUIDE ? 3 : which == CLD_KERNEL_CONV5 ? 4 : (which == CLD_KERNEL_UNET ? 7 : 2))) return fail(h, CLD_ERR_ARG, "cld_debug_force_kernel: bad argument");
     h->force_kernel[which] = form;
     return CLD_OK;
 }
@@ -1274,42 +1274,24 @@ int cld_finalize(cld_handle h, void* stream) {
             std::vector<float> packed = pack_conv_weights(wget, cout, cin, kh * kh);
             UP(l.wfrag, packed);
             l.kh = kh; l.stride = stride; l.hin = hin; l.cin = cin; l.cout = cout;
-            if (kh == 3 && stride == 1 && cin == cout) {
-                // Winograd F(2x2, 3x3): U[xi = 4 i + j][ci][co] = (G g G^T)[i][j], G = [1 0 0; .5 .5 .5; .5 -.5 .5; 0 0 1], formed in double
-                static const double Gm[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
-                std::vector<float> U((size_t)16 * cin * cout);
+            if (kh == 3 && stride == 1 && cin == cout && wino44_supported(hin, cout)) {
+                // Winograd F(4x4, 3x3) at the points {0, 1, -1, 1/2, -2, inf} (wino44_kernels.hip): U[xi = 6 i + j] = (G g G^T)[i][j], in double
+                static const double G6[6][3] = {{1, 0, 0}, {1.0 / 3, 1.0 / 3, 1.0 / 3}, {-1.0 / 3, 1.0 / 3, -1.0 / 3},
+                                                {-16.0 / 15, -8.0 / 15, -4.0 / 15}, {1.0 / 15, -2.0 / 15, 4.0 / 15}, {0, 0, 1}};
+                std::vector<float> U6((size_t)36 * cin * cout);
                 for (int co = 0; co < cout; ++co)
                     for (int ci = 0; ci < cin; ++ci) {
                         const float* g = &W[((size_t)co * cin + ci) * 9];
-                        double t[4][3];
-                        for (int i = 0; i < 4; ++i)
-                            for (int b = 0; b < 3; ++b) t[i][b] = Gm[i][0] * g[b] + Gm[i][1] * g[3 + b] + Gm[i][2] * g[6 + b];
-                        for (int i = 0; i < 4; ++i)
-                            for (int j = 0; j < 4; ++j)
-                                U[((size_t)(4 * i + j) * cin + ci) * cout + co] = (float)(t[i][0] * Gm[j][0] + t[i][1] * Gm[j][1] + t[i][2] * Gm[j][2]);
+                        double t[6][3];
+                        for (int i = 0; i < 6; ++i)
+                            for (int bb = 0; bb < 3; ++bb) t[i][bb] = G6[i][0] * g[bb] + G6[i][1] * g[3 + bb] + G6[i][2] * g[6 + bb];
+                        for (int i = 0; i < 6; ++i)
+                            for (int j = 0; j < 6; ++j)
+                                U6[((size_t)(6 * i + j) * cin + ci) * cout + co] = (float)(t[i][0] * G6[j][0] + t[i][1] * G6[j][1] + t[i][2] * G6[j][2]);
                     }
-                auto uget = [&](int co, int ci, int xi) -> float { return U[((size_t)xi * cin + ci) * cout + co]; };
-                std::vector<float> upacked = pack_conv_weights(uget, cout, cin, 16);
-                UP(l.ufrag, upacked);
-                if (wino44_supported(hin, cout)) {
-                    // Winograd F(4x4, 3x3) at the points {0, 1, -1, 1/2, -2, inf} (wino44_kernels.hip): U[xi = 6 i + j] = (G g G^T)[i][j], in double
-                    static const double G6[6][3] = {{1, 0, 0}, {1.0 / 3, 1.0 / 3, 1.0 / 3}, {-1.0 / 3, 1.0 / 3, -1.0 / 3},
-                                                    {-16.0 / 15, -8.0 / 15, -4.0 / 15}, {1.0 / 15, -2.0 / 15, 4.0 / 15}, {0, 0, 1}};
-                    std::vector<float> U6((size_t)36 * cin * cout);
-                    for (int co = 0; co < cout; ++co)
-                        for (int ci = 0; ci < cin; ++ci) {
-                            const float* g = &W[((size_t)co * cin + ci) * 9];
-                            double t[6][3];
-                            for (int i = 0; i < 6; ++i)
-                                for (int bb = 0; bb < 3; ++bb) t[i][bb] = G6[i][0] * g[bb] + G6[i][1] * g[3 + bb] + G6[i][2] * g[6 + bb];
-                            for (int i = 0; i < 6; ++i)
-                                for (int j = 0; j < 6; ++j)
-                                    U6[((size_t)(6 * i + j) * cin + ci) * cout + co] = (float)(t[i][0] * G6[j][0] + t[i][1] * G6[j][1] + t[i][2] * G6[j][2]);
-                        }
-                    auto u6get = [&](int co, int ci, int xi) -> float { return U6[((size_t)xi * cin + ci) * cout + co]; };
-                    std::vector<float> u6packed = pack_conv_weights(u6get, cout, cin, 36);
-                    UP(l.ufrag44, u6packed);
-                }
+                auto u6get = [&](int co, int ci, int xi) -> float { return U6[((size_t)xi * cin + ci) * cout + co]; };
+                std::vector<float> u6packed = pack_conv_weights(u6get, cout, cin, 36);
+                UP(l.ufrag44, u6packed);
             }
             return fold_bn(bnname, &l.scale, &l.shift);
         };
@@ -1970,7 +1952,7 @@ constexpr size_t kActFloats = (size_t)56 * 56 * 64;          // largest post-poo
 // to a CU: n * (196 | 49 | 16 | 4) / 16 * (C / 64) at 56x56 / 28x28 / 14x14 / 7x7 -- at n = 256 that is 6.125 / 3.06 / 2 / 1 generations of 512; a last
 // generation that is 6 % full costs a whole one.  The pass size is the one that minimises the modelled generation count of the whole batch (a
 // generation of the four launch kinds lasts 1.5 / 2.7 / 4.3 / 8.5 units -- measured: 36 / 65 / 103 / 202 us --), with a fixed cost per pass for its
-// 27 launches.  (With CLD_FORM_WINOGRAD_F2 the counts of wino_kernels.hip differ; the pass size is a speed choice only.)
+// 27 launches.  (The pass size is a speed choice only: a row's result does not depend on it.)
 int context_pass_size(int B) {
     if (B <= kCtxChunk) return B;
     auto cost = [](int n) {
@@ -1986,14 +1968,12 @@ int context_pass_size(int B) {
     return best;
 }
 
-// The one dispatch of the encoder's convolutions, shared by cld_context_encode and cld_debug_context_layer: the form a test forced
-// (cld_debug_force_kernel(CLD_KERNEL_CONTEXT)) picks F(4x4, 3x3), F(2x2, 3x3) or the implicit GEMM for the stride-1 3x3 layers; the
-// stride-2 3x3 and the 1x1/2 layers have the implicit GEMM only.
+// The one dispatch of the encoder's convolutions, shared by cld_context_encode and cld_debug_context_layer: F(4x4, 3x3) for the stride-1
+// 3x3 layers unless a test forced the direct form (cld_debug_force_kernel(CLD_KERNEL_CONTEXT)), the implicit GEMM otherwise and for the
+// stride-2 3x3 and the 1x1/2 layers.
 hipError_t context_conv(cld_handle h, const cld_handle_s::Conv2dLayer& l, const float* x, const float* res, float* y, int relu, int n, hipStream_t s) {
-    const bool wino = h->force_kernel[CLD_KERNEL_CONTEXT] != CLD_FORM_DIRECT;
-    const bool wino44 = h->force_kernel[CLD_KERNEL_CONTEXT] != CLD_FORM_WINOGRAD_F2;      // F(4x4, 3x3) at all four map sizes unless F(2x2) is forced
-    if (wino && wino44 && l.ufrag44) return launch_wino44_conv(l.hin, l.cout, WinoArgs{x, l.ufrag44, l.scale, l.shift, res, y, n, relu}, s);
-    if (wino && l.ufrag) return launch_wino_conv(l.hin, l.cout, WinoArgs{x, l.ufrag, l.scale, l.shift, res, y, n, relu}, s);
+    if (h->force_kernel[CLD_KERNEL_CONTEXT] != CLD_FORM_DIRECT && l.ufrag44)
+        return launch_wino44_conv(l.hin, l.cout, WinoArgs{x, l.ufrag44, l.scale, l.shift, res, y, n, relu}, s);
     return launch_conv2d(l.kh, l.stride, l.hin, x, l.wfrag, l.scale, l.shift, res, y, n, l.cin, l.cout, relu, s);
 }
 

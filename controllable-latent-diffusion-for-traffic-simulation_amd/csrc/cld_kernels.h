@@ -428,8 +428,8 @@ hipError_t launch_maxpool(const float* x, float* y, int B, hipStream_t s);
 // hin = input height = width in {56, 28, 14, 7}; wfrag in pack_conv_weights layout (tap = kh * KW + kw)
 hipError_t launch_conv2d(int kh, int stride, int hin, const float* x, const float* wfrag, const float* scale,
                          const float* shift, const float* res, float* y, int B, int cin, int cout, int relu, hipStream_t s);
-// 3x3 / stride 1 / pad 1 convolution with C_in = C_out by Winograd F(2x2, 3x3) (wino_kernels.hip) + folded BatchNorm [+ residual]
-// [+ ReLU]; ufrag: U = G g G^T in pack_conv_weights layout with the 16 transform-domain positions as "taps"; B <= 256
+// 3x3 / stride 1 / pad 1 convolution with C_in = C_out by Winograd F(4x4, 3x3) (wino44_kernels.hip) + folded BatchNorm [+ residual]
+// [+ ReLU]; ufrag: U = G g G^T in pack_conv_weights layout with the 36 transform-domain positions as "taps" (Conv2dLayer::ufrag44); B <= 256
 struct WinoArgs {
     const float* x;        // [B, H, H, C] NHWC
     const float* ufrag;
@@ -439,8 +439,6 @@ struct WinoArgs {
     float* y;              // [B, H, H, C]
     int B, relu;
 };
-hipError_t launch_wino_conv(int hin, int channels, const WinoArgs& a, hipStream_t s);
-// the same layers at 56x56 / 28x28 by F(4x4, 3x3) (wino44_kernels.hip): a.ufrag = the 36-plane fragments (Conv2dLayer::ufrag44)
 bool wino44_supported(int hin, int channels);
 hipError_t launch_wino44_conv(int hin, int channels, const WinoArgs& a, hipStream_t s);
 struct ContextHeadArgs {

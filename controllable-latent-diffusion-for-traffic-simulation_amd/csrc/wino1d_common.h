@@ -37,7 +37,7 @@ namespace {
 
 __device__ __forceinline__ v4f fma4(const v4f a, const float s, const v4f b) { return __builtin_elementwise_fma(a, v4f{s, s, s, s}, b); }      // a s + b
 
-__device__ __forceinline__ int hsw1(int k) { return ((k & 1) * 3) ^ (k >> 1); }      // wino_kernels.hip hsw
+__device__ __forceinline__ int hsw1(int k) { return ((k & 1) * 3) ^ (k >> 1); }      // slot permutation of the 16-byte channel quads inside a 64-byte V row: {0, 3, 1, 2}
 
 #define W1_DPP(v, ctrl) __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), ctrl, 0xf, 0xf, false))
 // sum over the 4 lanes of a quad (the four tiles of an agent) and the 4 lane groups (channel quads), left in every lane involved

@@ -21,10 +21,10 @@
 // 5 x 13: 2.03x fewer.  Rounding: 9e-7 of max|y| against fp64 on unit-variance data, the direct form 6e-7 (one-dimensional transforms
 // do not square the constants the way F(4x4, 3x3) does).
 //
-// Kernel (the structure of wino_kernels.hip): a workgroup owns 16 agents = 64 rows = four M-tiles x 64 output channels x the 8 xi;
-// wave w holds the 32 accumulators of channels 16 w .. 16 w + 15; the filters are the MFMA's A operand and the rows its B operand, so
+// Kernel: a workgroup owns half of a group of 16 agents (8 at L = 26) = 32 rows = two M-tiles x 64 output channels x the 8 xi;
+// wave w holds the 16 accumulators of channels 16 w .. 16 w + 15; the filters are the MFMA's A operand and the rows its B operand, so
 // a lane ends up with four consecutive channels of one (agent, tile).  Per 16-channel chunk a thread fetches the 8 input rows of one
-// (agent, tile) x four channels (eight 16-byte loads, issued two blocks' worth of latency ahead), applies B^T in the shadow of the
+// (agent, tile) x two channels (eight 8-byte loads, issued two blocks' worth of latency ahead), applies B^T in the shadow of the
 // MFMAs and writes V[xi][row][16 channels] into one of two LDS images (64-byte rows, 16-byte slots permuted so the four 16-lane groups
 // of a ds_read_b128 touch every bank once).  U comes from L2 in MFMA fragment order (pack_conv_weights with xi as the tap), four items
 // ahead.  Epilogue in registers: A^T, conv bias, two-pass GroupNorm statistics (a group = 32 channels = two waves: DPP + permlane
@@ -58,7 +58,8 @@ struct W1Geo {
     static constexpr int ROWS = AG * TPA;
     static constexpr int KC = 16, NCH = CIN / KC, NC1 = CS / KC, NCB = COUT / 64, NTN = COUT / 16;
     static constexpr int GS = COUT / 8;                // GroupNorm group: 32 channels = two waves, 16 = one, 8 = half of one
-    static constexpr int VBUF = 8 * 64 * KC;           // floats per V image
+    static constexpr int NM = 2;                       // M-tiles of an item: half of the group's four
+    static constexpr int VBUF = 8 * 16 * NM * KC;      // floats per V image: 8 xi x 16 NM rows x 16 channels
     static constexpr int XCH = 2 * 4 * 2 * 64;         // exchange scratch behind the images: [pass][wave][group of the wave][row]
     static constexpr size_t LDS_BYTES = (2 * VBUF + XCH) * sizeof(float);
     static_assert(TPA == 4 || TPA == 7, "L = 13 or 26");
@@ -70,12 +71,12 @@ struct W1Geo {
 
 }  // namespace
 
-// One item: NM M-tiles (4 = a whole agent group, 2 = half of one) x the 64 output channels of block cb, agents b0 ..
-template <int L, int CIN, int CS, int COUT, int NM>
+// One half item: NM = 2 of an agent group's four M-tiles x the 64 output channels of block cb, agents b0 ..
+template <int L, int CIN, int CS, int COUT>
 __device__ __forceinline__ void wino1d_item(const ConvArgs& p, const int b_pad, const int cb, const int b0, float* lds1) {
     typedef W1Geo<L, CIN, CS, COUT> G;
+    constexpr int NM = G::NM, VB = G::VBUF;
     constexpr int ROWS = G::ROWS * NM / 4;             // live rows of the item (at L = 26 the rest of its last M-tile idles)
-    constexpr int VB = 8 * 16 * NM * G::KC;             // floats per V image of this item: 8 xi x 16 NM rows x 16 channels (a half item's images are half as large)
     float* xch = lds1 + 2 * VB;                        // GroupNorm sums meet here: two waves of a 32-channel group; the rows of an agent at L = 26
     const int tid = threadIdx.x, lane = tid & 63, i16 = lane & 15, kk = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -88,12 +89,12 @@ __device__ __forceinline__ void wino1d_item(const ConvArgs& p, const int b_pad, 
     }
 #endif
 
-    // ---- staging role: row rs = (agent rs / TPA, tile rs % TPA); a whole item: 64 rows x four channels of the chunk per thread (16-byte
-    //      loads); a half item: 32 rows x TWO channels (8-byte loads), so that all four waves stage there as well -- with the 16-byte map
-    //      waves 2, 3 of a half item had nothing to stage and waited at every chunk barrier for waves 0, 1 ----
-    constexpr int SW = NM == 4 ? 4 : 2;                // channels per staging thread
+    // ---- staging role: row rs = (agent rs / TPA, tile rs % TPA): 32 rows x TWO channels of the chunk per thread (8-byte loads), so that
+    //      all four waves stage -- with four channels per thread (16-byte loads) waves 2, 3 have nothing to stage and wait at every chunk
+    //      barrier for waves 0, 1 ----
+    constexpr int SW = 2;                              // channels per staging thread
     typedef float vS __attribute__((ext_vector_type(SW)));
-    const int rs = NM == 4 ? tid >> 2 : tid >> 3, cq = NM == 4 ? tid & 3 : tid & 7;
+    const int rs = tid >> 3, cq = tid & 7;
     const int total_bytes = b_pad * L * CS * 4;
     const __amdgpu_buffer_rsrc_t rsx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x1), 0, total_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsx2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(CS == CIN ? p.x1 : p.x2), 0, total_bytes, 0x00020000);
@@ -108,15 +109,14 @@ __device__ __forceinline__ void wino1d_item(const ConvArgs& p, const int b_pad, 
     }
     vS d[8];
     auto ld = [&](const __amdgpu_buffer_rsrc_t r, const int vo, const int so) {
-        if constexpr (SW == 4) return __builtin_bit_cast(vS, __builtin_amdgcn_raw_buffer_load_b128(r, vo, so, 0));
-        else return __builtin_bit_cast(vS, __builtin_amdgcn_raw_buffer_load_b64(r, vo, so, 0));
+        return __builtin_bit_cast(vS, __builtin_amdgcn_raw_buffer_load_b64(r, vo, so, 0));
     };
     auto patch_load = [&](const int i, const int c) {
         if (CS == CIN || c < G::NC1) d[i] = ld(rsx, voff[i], c * (G::KC * 4));
         else d[i] = ld(rsx2, voff[i], (c - G::NC1) * (G::KC * 4));
     };
-    const int c4 = NM == 4 ? cq : cq >> 1;              // the 16-byte slot of the row
-    const int wofs = rs * 16 + ((((rs >> 2) & 3) ^ hsw1(c4)) << 2) + (NM == 4 ? 0 : (cq & 1) * 2);
+    const int c4 = cq >> 1;                             // the 16-byte slot of the row
+    const int wofs = rs * 16 + ((((rs >> 2) & 3) ^ hsw1(c4)) << 2) + (cq & 1) * 2;
     auto fmaS = [](const vS a, const float sc, const vS b) {
         vS sv;
 #pragma unroll
@@ -364,21 +364,18 @@ __device__ __forceinline__ void wino1d_item(const ConvArgs& p, const int b_pad, 
     W1STAMP_RT(9);
 }
 
-// Workgroup id -> item.  Whole items (a 16-agent group at L = 13, 8 agents at L = 26) when there are at least 512 of them -- two per CU;
-// below that every group is split into two half items (two M-tiles each: twice the U traffic per MFMA, but a second wave on every SIMD:
-// at 1,024 rows 256 whole items leave every CU with one workgroup).  ids x, x + 8, x + 16, x + 24 (whole) resp. 2 x the same (halves) are
-// the channel blocks of one agent group: one XCD, back to back.
-// Two instantiations per layer shape: whole items (128 accumulator registers: two workgroups per CU) and half items, which need half the
-// accumulators and half the LDS (36 KB) -- WINO1D_HALF_WGS workgroups per CU.
+// Workgroup id -> item: every agent group (16 agents at L = 13, 8 at L = 26) is two half items (two M-tiles each: twice the U traffic per MFMA
+// of a whole item, but a second wave on every SIMD for launches that leave a CU with one whole item); ids 2 x (x, x + 8, x + 16, x + 24) are
+// the channel blocks of one agent group: one XCD, back to back.  Half the accumulators of a whole item and 36 KB of LDS: WINO1D_HALF_WGS
+// workgroups per CU.
 #ifndef WINO1D_HALF_WGS
 #define WINO1D_HALF_WGS 2
 #endif
-template <int L, int CIN, int CS, int COUT, int HALVES>
-__global__ __launch_bounds__(256, HALVES ? WINO1D_HALF_WGS : 2) void wino1d_conv_kernel(const ConvArgs p, const int b_pad, const int xcd_map) {
+template <int L, int CIN, int CS, int COUT>
+__global__ __launch_bounds__(256, WINO1D_HALF_WGS) void wino1d_conv_kernel(const ConvArgs p, const int b_pad, const int xcd_map) {
     typedef W1Geo<L, CIN, CS, COUT> G;
     extern __shared__ __attribute__((aligned(16))) float lds1[];
-    constexpr int halves = HALVES;
-    const int e = halves ? blockIdx.x >> 1 : blockIdx.x, half = halves ? (int)(blockIdx.x & 1) : -1;
+    const int e = blockIdx.x >> 1, half = (int)(blockIdx.x & 1);
     int cb, grp;
     if (xcd_map) {
         cb = (e >> 3) % G::NCB;
@@ -387,8 +384,7 @@ __global__ __launch_bounds__(256, HALVES ? WINO1D_HALF_WGS : 2) void wino1d_conv
         cb = e % G::NCB;
         grp = e / G::NCB;
     }
-    if constexpr (!HALVES) wino1d_item<L, CIN, CS, COUT, 4>(p, b_pad, cb, grp * G::AG, lds1);
-    else wino1d_item<L, CIN, CS, COUT, 2>(p, b_pad, cb, grp * G::AG + half * (G::AG / 2), lds1);
+    wino1d_item<L, CIN, CS, COUT>(p, b_pad, cb, grp * G::AG + half * (G::AG / 2), lds1);
 }
 
 bool wino1d_supported(int l_in, int c1, int c2, int c_out) {
@@ -405,9 +401,6 @@ long wino1d_gemm_rows(int l_in, int b_pad) { return l_in == 13 ? 4L * b_pad : 8L
 // below one generation and when the last generation would be at most half full (752 whole items are two rounds, 1,504 halves one and a
 // half).  Whole items run in wino1d_edge.hip's form (the ragged end of the sequence direct: 27 / 28 MFMAs per row where the items of
 // this file issue 32), half items here.
-#ifndef WINO1D_EDGE
-#define WINO1D_EDGE 1
-#endif
 static bool takes_halves(int l_in, int c_out, int b_pad) {
     const int nfull = b_pad / (l_in == 13 ? 16 : 8) * (c_out / 64);
     const int tail = nfull % WINO1D_HALVES_BELOW;
@@ -424,7 +417,6 @@ static bool takes_ksplit(int l_in, int c_out, int b_pad) {
 }
 // 0: half items, 1: whole items, 2: whole items of eight waves
 static int item_form_of(int l_in, int c_out, int b_pad, int forced) {
-    if (!WINO1D_EDGE) return takes_halves(l_in, c_out, b_pad) ? 0 : 3;
     if (forced) return forced;
     if (takes_ksplit(l_in, c_out, b_pad)) return 2;
     return takes_halves(l_in, c_out, b_pad) ? 0 : 1;
@@ -440,21 +432,16 @@ static hipError_t launch_wino1d_inst(const ConvArgs& a, int b_pad, int item_form
     typedef W1Geo<L, CIN, CS, COUT> G;
     const int groups = b_pad / G::AG, nfull = groups * G::NCB;
     const int form = item_form_of(L, COUT, b_pad, item_form);
-    const bool halves = form == 0;
-    if (form == 1 || form == 2) {
+    if (form != 0) {
         ConvArgs e = a;
         e.wfrag = a.wfrag_edge;
         return e.wfrag ? launch_wino1d_edge(e, L, b_pad, form == 2, s) : hipErrorInvalidValue;
     }
-    auto kern_whole = wino1d_conv_kernel<L, CIN, CS, COUT, 0>;
-    auto kern_half = wino1d_conv_kernel<L, CIN, CS, COUT, 1>;
-    constexpr size_t lds_half = (2 * (G::VBUF / 2) + G::XCH) * sizeof(float);
-    static unsigned long long attr_done = 0, attr_done_h = 0;      // one bit per device (a second handle on another device sets it there too)
-    if (hipError_t e = set_max_lds_once(reinterpret_cast<const void*>(kern_whole), (int)G::LDS_BYTES, &attr_done); e != hipSuccess) return e;
-    if (hipError_t e = set_max_lds_once(reinterpret_cast<const void*>(kern_half), (int)lds_half, &attr_done_h); e != hipSuccess) return e;
+    auto kern = wino1d_conv_kernel<L, CIN, CS, COUT>;
+    static unsigned long long attr_done = 0;      // one bit per device (a second handle on another device sets it there too)
+    if (hipError_t e = set_max_lds_once(reinterpret_cast<const void*>(kern), (int)G::LDS_BYTES, &attr_done); e != hipSuccess) return e;
     if ((long)b_pad * L * CS * 4 >= (1L << 31) || (long)b_pad * L * COUT * 4 >= (1L << 31)) return hipErrorInvalidValue;      // byte offsets are 32-bit
-    if (halves) hipLaunchKernelGGL(kern_half, dim3(nfull << 1), dim3(256), lds_half, s, a, b_pad, groups % 8 == 0 ? 1 : 0);
-    else hipLaunchKernelGGL(kern_whole, dim3(nfull), dim3(256), G::LDS_BYTES, s, a, b_pad, groups % 8 == 0 ? 1 : 0);
+    hipLaunchKernelGGL(kern, dim3(nfull << 1), dim3(256), G::LDS_BYTES, s, a, b_pad, groups % 8 == 0 ? 1 : 0);
     return hipGetLastError();
 }
 

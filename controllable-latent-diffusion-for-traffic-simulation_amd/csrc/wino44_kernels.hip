@@ -2,8 +2,9 @@
 // 512 @ 7x7; reference: torchvision resnet18 built at src/tbsim/models/base_models.py:559-614, called from models/context_utils.py:40-61) by
 // Winograd's minimal filtering F(4x4, 3x3).
 //
-// wino_kernels.hip runs these layers as F(2x2, 3x3): 16 multiplies per 2x2 outputs, 2.25x fewer than the direct form.  On 4x4 tiles the same
-// construction needs 36 multiplies per 16 outputs: **4x fewer than the direct form, 1.78x fewer MFMAs than F(2x2, 3x3)** where the map is a
+// As implicit GEMMs (context_kernels.hip conv2d_kernel) these layers keep the fp32 MFMA pipe busy 85-98 % of the time: what is left to take out
+// is the arithmetic.  F(2x2, 3x3) needs 16 multiplies per 2x2 outputs, 2.25x fewer than the direct form; on 4x4 tiles the same construction
+// needs 36 multiplies per 16 outputs: **4x fewer than the direct form, 1.78x fewer MFMAs than F(2x2, 3x3)** where the map is a
 // whole number of tiles (56x56: 14 x 14 tiles, 28x28: 7 x 7) and at 7x7 (2 x 2 tiles over 8x8, which F(2x2) covers too), 1.36x at 14x14 (4 x 4 tiles
 // over 16x16).  What decides whether that is usable in fp32 is the choice of points.  With
 // {0, +-1, +-2, inf} (the textbook set) or {0, +-1, +-1/2, inf} the rounding error of a 64-channel layer is 4 - 9e-6 of max|y| against
@@ -18,12 +19,13 @@
 //     Y = A^T [ (G g G^T) (.) (B^T d B) ] A   for the 6x6 input patch d (rows / columns 4 t - 1 .. 4 t + 4) of a 4x4 output tile;
 // every entry of B^T and A^T is exact in fp32, U = G g G^T is formed in double at cld_finalize.
 //
-// Kernel (the structure of wino_kernels.hip): a workgroup owns 16 tiles (one M-tile; tiles are a flat list over the pass's agents) x 64
+// Kernel: a workgroup owns 16 tiles (one M-tile; tiles are a flat list over the pass's agents) x 64
 // output channels x all 36 xi: wave w holds the 36 accumulators (144 registers) of channels 16 w .. 16 w + 15; filters are the MFMA's A
 // operand, tiles its B operand, so a lane ends up with four consecutive channels of the 16 outputs of ONE tile and the output transform
 // runs in registers.  Per 16-channel chunk a thread fetches the 6x6 patch of one (tile, channel) straight from the NHWC tensor (36 4-byte
 // loads, the 16 channels of a tile are one 64-byte segment), applies d B two rows at a time on register pairs and B^T (.) column by column,
-// and writes V[xi][tile][16 channels] into one of two LDS images (36 KB each; 64-byte rows, 16-byte slots permuted as in wino_kernels.hip).
+// and writes V[xi][tile][16 channels] into one of two LDS images (36 KB each; 64-byte rows, 16-byte slots permuted by hsw4 so that
+// the four 16-lane groups of a ds_read_b128 touch every bank once).
 // U comes from L2 in MFMA fragment order (pack_conv_weights with xi as the "tap"), four (xi, chunk) items ahead.  One barrier per chunk, two
 // workgroups per CU.  What bounds it (scripts/ubench/w44_unit.hip): not the MFMAs (44 % busy) but the ~400 instructions per
 // thread and chunk of fetching and transforming a patch, which only the OTHER workgroup's MFMAs can cover -- a variant with eight waves per
@@ -35,7 +37,7 @@
 #endif
 
 
-// (wino_kernels.hip) a tile's result must not depend on its place in the workgroup: no implicit contraction
+// a tile's result must not depend on its place in the workgroup: no implicit contraction
 #pragma clang fp contract(off)
 
 namespace cld {
@@ -74,7 +76,7 @@ struct W44Geo {
     static_assert(NCH % 2 == 0, "chunk pairs are unrolled");
 };
 
-__device__ __forceinline__ int hsw4(int k) { return ((k & 1) * 3) ^ (k >> 1); }      // wino_kernels.hip hsw
+__device__ __forceinline__ int hsw4(int k) { return ((k & 1) * 3) ^ (k >> 1); }      // slot permutation of the 16-byte channel quads inside a 64-byte V row: {0, 3, 1, 2}
 
 // t = B^T d (or a row of d B: B^T applied along the other index) for six values
 __device__ __forceinline__ void bt6(const float d0, const float d1, const float d2, const float d3, const float d4, const float d5, float (&t)[6]) {
@@ -126,7 +128,7 @@ __global__ __launch_bounds__(256, 2) void wino44_conv_kernel(const WinoArgs p) {
     // Byte offsets (unsigned 32-bit) are taken from patch element (1, 1) -- the tile's first output position, always inside the image, so the
     // vector offset of every load is a valid non-negative offset by itself (the range check does not see the scalar offset).  Rows and
     // columns 1 .. 4 of a patch are always inside: their distances ride in the scalar offset (rows) and the instruction's immediate (columns);
-    // row 0 / 5 and column 0 / 5 can be the zero padding and keep an offset of their own, 2^30 when they are (wino_kernels.hip: past the
+    // row 0 / 5 and column 0 / 5 can be the zero padding and keep an offset of their own, 2^30 when they are (past the
     // tensor's <= 206 MB, the range check returns 0); so does every element of a tile past the end of the list
     constexpr unsigned kOut = 1u << 30;
     constexpr int ROWB = HIN * G::C * 4, COLB = G::C * 4;           // bytes between patch rows / columns

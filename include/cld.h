@@ -995,8 +995,8 @@ int cld_debug_lds_floor(cld_handle h, size_t bytes);
 #define CLD_KERNEL_UNET 3     /* the 64-channel levels of a U-Net evaluation: CLD_FORM_AUTO by batch size, CLD_FORM_LAYERS one launch
                                * per layer (conv_block.hip), CLD_FORM_CHAIN the LDS-resident layer chains (conv_chain.hip) */
 #define CLD_KERNEL_CONTEXT 4  /* the 3x3 / stride-1 convolutions of the ContextEncoder: CLD_FORM_AUTO / CLD_FORM_WINOGRAD Winograd F(4x4, 3x3)
-                               * at all four map sizes (wino44_kernels.hip), CLD_FORM_WINOGRAD_F2 F(2x2, 3x3) (wino_kernels.hip), CLD_FORM_DIRECT
-                               * the implicit-GEMM kernel the other convolutions use (and the stem with a separate max-pool launch) */
+                               * at all four map sizes (wino44_kernels.hip), CLD_FORM_DIRECT the implicit-GEMM kernel the other convolutions
+                               * use (and the stem with a separate max-pool launch) */
 #define CLD_KERNEL_CONV5 5    /* the Conv1d(k5) + GroupNorm + Mish launches of the L = 13 / 26 levels of a U-Net evaluation (exact-fp32 handles): CLD_FORM_AUTO
                                * by batch size, CLD_FORM_DIRECT conv_block.hip, CLD_FORM_WINOGRAD Winograd F(4, 5) (wino1d_edge.hip / wino1d_kernels.hip by launch size),
                                * CLD_FORM_WINOGRAD_WHOLE wino1d_edge.hip at every size */
@@ -1015,8 +1015,6 @@ int cld_debug_lds_floor(cld_handle h, size_t bytes);
 #define CLD_FORM_CHAIN_WINO1 7   /* CLD_KERNEL_UNET only: the Winograd chains with one-agent tiles: CLD_FORM_AUTO / CLD_FORM_CHAIN up to 944 rows */
 #define CLD_FORM_DIRECT 1     /* CLD_KERNEL_CONTEXT, CLD_KERNEL_CONV5 */
 #define CLD_FORM_WINOGRAD 2   /* CLD_KERNEL_CONTEXT, CLD_KERNEL_CONV5 */
-#define CLD_FORM_WINOGRAD_F2 3  /* CLD_KERNEL_CONTEXT only: F(2x2, 3x3) for every stride-1 3x3 convolution (wino_kernels.hip); CLD_FORM_AUTO / CLD_FORM_WINOGRAD
-                                 * take F(4x4, 3x3) (wino44_kernels.hip) */
 #define CLD_FORM_WINOGRAD_KSPLIT 4  /* CLD_KERNEL_CONV5 only: whole items run by eight waves (the two halves of the input channels on four waves each) at every
                                      * launch size: what CLD_FORM_WINOGRAD takes by itself for launches of about one whole item per CU */
 #define CLD_FORM_WINOGRAD_WHOLE 3   /* CLD_KERNEL_CONV5 only: Winograd with whole items at every launch size (wino1d_edge.hip: what CLD_FORM_WINOGRAD takes
@@ -1026,7 +1024,7 @@ int cld_debug_force_kernel(cld_handle h, int32_t which, int32_t form);
 /* Tests only: one layer of the ContextEncoder's ResNet-18 on n agents (1 <= n <= 256, one pass of cld_context_encode), through the same
  * dispatch cld_context_encode uses, in the form cld_debug_force_kernel(CLD_KERNEL_CONTEXT, ...) holds: CLD_FORM_DIRECT the stem and a
  * separate max-pool launch and the implicit GEMM for every convolution; CLD_FORM_AUTO / CLD_FORM_WINOGRAD the stem with the fused max-pool
- * and F(4x4, 3x3) for the thirteen stride-1 3x3 layers; CLD_FORM_WINOGRAD_F2 the fused stem and F(2x2, 3x3).  `layer`:
+ * and F(4x4, 3x3) for the thirteen stride-1 3x3 layers.  `layer`:
  *   0       the stem: x = image [n,34,224,224] NCHW -> y = maxpool(relu(bn(conv7x7/2 x))) [n,56,56,64] NHWC (residual NULL, relu 1)
  *   1..16   rn_conv[li][b][c] in forward order (layer = 1 + 4 li + 2 b + c: layer{li+1}.{b}.conv{c+1} + bn{c+1})
  *   17..19  the 1x1/2 downsample convolutions + BatchNorm of layer2 / layer3 / layer4
@@ -1034,7 +1032,7 @@ int cld_debug_force_kernel(cld_handle h, int32_t which, int32_t form);
  * Synchronous for the direct stem (it allocates its [n,112,112,64] scratch). */
 int cld_debug_context_layer(cld_handle h, int32_t layer, const float* x, const float* residual, float* y, int32_t n, int32_t relu,
                             void* stream);
-/* Agents per pass cld_context_encode takes for B agents in its Winograd forms (no handle, no device call; tests): B for B <= 256, else a pass
+/* Agents per pass cld_context_encode takes for B agents in its Winograd form (no handle, no device call; tests): B for B <= 256, else a pass
  * size in [128, 256] -- passes of that size and a last one of the rest.  The direct form runs passes of 256.  < 0: bad argument. */
 int cld_debug_context_pass_size(int32_t B);
 

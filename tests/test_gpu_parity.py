@@ -318,10 +318,9 @@ def test_context_encoder_vs_oracle(eng_ctx, B, dense):
 
 @pytest.mark.parametrize("B", [1, 5, 67])
 def test_context_winograd_and_direct_convolutions_agree(eng_ctx, B):
-    """The 3x3 / stride-1 convolutions of the ResNet-18 run as Winograd F(4x4, 3x3) (wino44_kernels.hip) at all four map sizes by default,
-    as F(2x2, 3x3) (wino_kernels.hip) and as the implicit GEMM of the other convolutions on request: three kernels, one function.  Ragged
-    tile lists (B = 1: 196 / 49 / 16 / 4 tiles of 4x4 outputs in workgroups of 16, 784 / 196 / 49 / 16 tiles of 2x2 outputs in workgroups
-    of 32; the 14x14 and 7x7 maps' last 4x4 tiles and the 7x7 map's last 2x2 tiles hang over the edge), against each other and the oracle."""
+    """The 3x3 / stride-1 convolutions of the ResNet-18 run as Winograd F(4x4, 3x3) (wino44_kernels.hip) at all four map sizes by default
+    and as the implicit GEMM of the other convolutions on request: two kernels, one function.  Ragged tile lists (B = 1: 196 / 49 / 16 / 4
+    tiles of 4x4 outputs in workgroups of 16; the 14x14 and 7x7 maps' last tiles hang over the edge), against each other and the oracle."""
     from oracle import cld_oracle as O
     img = torch.from_numpy(synth.make_raster(B, 13, dense=True))
     cs = torch.from_numpy(synth.make_inputs(B, 13)["curr_states"])
@@ -339,18 +338,7 @@ def test_context_winograd_and_direct_convolutions_agree(eng_ctx, B):
     scale = float(md.abs().max())
     assert float((md - mw).abs().max()) <= 2e-5 * scale
     assert float((cd - cw).abs().max()) <= 2e-5
-    # the Winograd form runs every stride-1 3x3 layer as F(4x4, 3x3) (wino44_kernels.hip); F(2x2, 3x3) for every layer on request: a third
-    # kernel set, the same function to the same bars (tests/test_gpu_context.py holds each layer of each form to float64 per element)
-    try:
-        eng_ctx.force_kernel("context", "winograd_f2")
-        c2, m2 = eng_ctx.context_encode(img.cuda(), cs.cuda(), want_map_feat=True)
-        c2, m2 = c2.clone(), m2.clone()
-    finally:
-        eng_ctx.force_kernel("context", "auto")
-    assert not torch.equal(m2, mw)
-    print(f"context B={B}: max|F(4x4) - direct| = {float((md - mw).abs().max()) / scale:.2e}, max|F(2x2) - direct| = {float((md - m2).abs().max()) / scale:.2e} of max|map_feat|")
-    assert float((m2 - mw).abs().max()) <= 2e-5 * scale and float((md - m2).abs().max()) <= 2e-5 * scale
-    assert float((c2 - cw).abs().max()) <= 2e-5
+    print(f"context B={B}: max|F(4x4) - direct| = {float((md - mw).abs().max()) / scale:.2e} of max|map_feat|")
     if B <= 5:
         taps = {}
         ref = O.context_encode(O.to_torch(synth.make_context_weights(0)), img, cs, taps)

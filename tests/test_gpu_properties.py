@@ -171,6 +171,13 @@ def test_abi_error_paths(eng):
     assert lib.cld_load_weight(h, b"betas", w.ctypes.data, 4) == 0                            # schedule keys ignored
     assert lib.cld_finalize(h, None) == -2 and b"missing weight" in lib.cld_last_error(h)
     assert lib.cld_unet_forward(h, p(x), p(cond), 5, p(out), B, p(big), big.numel(), None) == -2
+    # cld_debug_force_kernel: every form a kernel has is accepted, the first number past them (for the ContextEncoder: 3) is refused
+    for kind, past in (("context", 3), ("unet", 8), ("conv5", 5), ("guide", 4), ("decode", 3)):
+        for form in sorted(_lib.KERNEL_FORMS[kind].values()):
+            assert lib.cld_debug_force_kernel(h, _lib.KERNELS[kind], form) == 0, (kind, form)
+        for form in (past, -1):
+            assert lib.cld_debug_force_kernel(h, _lib.KERNELS[kind], form) == -1, (kind, form)
+    assert lib.cld_debug_force_kernel(h, 6, 0) == -1
     assert lib.cld_destroy(h) == 0
     cfg.horizon = 40
     assert lib.cld_create(C.byref(cfg), C.byref(h)) == -1                                      # unsupported architecture

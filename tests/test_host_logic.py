@@ -210,17 +210,17 @@ def test_force_kernel_tables_match_header():
     for name, macro in kernels.items():
         assert _lib.KERNELS[name] == defs["CLD_KERNEL_" + macro], name
     forms = {"auto": "AUTO", "valu": "VALU", "mfma": "MFMA", "quad": "MFMA_QUAD", "layers": "LAYERS", "chain": "CHAIN", "chain1": "CHAIN_TILE1",
-             "chain4": "CHAIN_TILE4", "chainw": "CHAIN_WINO", "chainw2": "CHAIN_WINO2", "chainw1": "CHAIN_WINO1", "direct": "DIRECT", "winograd": "WINOGRAD", "winograd_whole": "WINOGRAD_WHOLE", "winograd_ksplit": "WINOGRAD_KSPLIT", "winograd_f2": "WINOGRAD_F2"}
+             "chain4": "CHAIN_TILE4", "chainw": "CHAIN_WINO", "chainw2": "CHAIN_WINO2", "chainw1": "CHAIN_WINO1", "direct": "DIRECT", "winograd": "WINOGRAD", "winograd_whole": "WINOGRAD_WHOLE", "winograd_ksplit": "WINOGRAD_KSPLIT"}
     assert set(_lib.FORMS) == set(forms)
     for name, macro in forms.items():
         assert _lib.FORMS[name] == defs["CLD_FORM_" + macro], name
     # per kernel: every (kernel, name) pair -> its macro, and the names a kernel does not have are refused (the numbers are reused across
-    # kernels: "winograd_f2" given for the k5 layers would silently run whole items)
+    # kernels: "winograd_whole" given for the guide kernel would silently run its "quad" form)
     per_kernel = {"guide": {"auto": "AUTO", "valu": "VALU", "mfma": "MFMA", "quad": "MFMA_QUAD"},
                   "decode": {"auto": "AUTO", "valu": "VALU", "mfma": "MFMA"}, "encode": {"auto": "AUTO", "valu": "VALU", "mfma": "MFMA"},
                   "unet": {"auto": "AUTO", "layers": "LAYERS", "chain": "CHAIN", "chain1": "CHAIN_TILE1", "chain4": "CHAIN_TILE4",
                            "chainw": "CHAIN_WINO", "chainw2": "CHAIN_WINO2", "chainw1": "CHAIN_WINO1"},
-                  "context": {"auto": "AUTO", "direct": "DIRECT", "winograd": "WINOGRAD", "winograd_f2": "WINOGRAD_F2"},
+                  "context": {"auto": "AUTO", "direct": "DIRECT", "winograd": "WINOGRAD"},
                   "conv5": {"auto": "AUTO", "direct": "DIRECT", "winograd": "WINOGRAD", "winograd_whole": "WINOGRAD_WHOLE",
                             "winograd_ksplit": "WINOGRAD_KSPLIT"}}
     assert set(_lib.KERNEL_FORMS) == set(per_kernel)
@@ -232,7 +232,7 @@ def test_force_kernel_tables_match_header():
             with pytest.raises(ValueError):
                 _lib.form_id(kind, name)
     with pytest.raises(ValueError):
-        _lib.form_id("conv5", "winograd_f2")
+        _lib.form_id("context", "winograd_whole")
     with pytest.raises(ValueError):
         _lib.form_id("nope", "auto")
 
